@@ -18,10 +18,17 @@ Contract (task statement): `python bench.py --gpus N --steps K --warmup W` print
   ways.  At N > 1 the weak line also carries the strong number as a nested object.
 
 Workload = BASELINE.json configs[1]: NPE + NSF, theta-dim 10, x-dim 10, 100 000 simulations, batch 65 536, sbi's
-default NSF hyper-parameters (98 025 parameters).  Nested objects: `log_prob` (M1, paired x) and
-`log_prob_broadcast_x` (M1, one x_o), `posterior_sample` (M3, 10^6 draws), `npe_train` (M2 exactly as SURVEY 8d
-defines it: `NPE.train()` on 100 000 simulations, batch 65 536, validation pass and early-stopping bookkeeping
-included), `fmpe_train` (configs[4] step).
+default NSF hyper-parameters (98 025 parameters).
+
+* A plain run (default `--mode both`, no `--full`) measures the headline train leg and nothing else.  `--full` adds
+  what the default line carried until now: nested objects `log_prob` (M1, paired x) and `log_prob_broadcast_x` (M1,
+  one x_o), `posterior_sample` (M3, 10^6 draws), `npe_train` (M2 exactly as SURVEY 8d defines it: `NPE.train()` on
+  100 000 simulations, batch 65 536, validation pass and early-stopping bookkeeping included), `fmpe_train`
+  (configs[4] step), `small_batch`, `npe_c_atomic`, `mcmc`, `rccl_1rank`, `strong_scaling` (N > 1) and the CPU
+  baselines.  Every other `--mode` runs as it always has; `--full` changes nothing there.
+* `--dump-outputs DIR` writes what the headline leg's LAST timed step computed as `DIR/<name>.npy` (float32).  The
+  train leg's state is rewound to its initial value after the untimed preheat (whose length depends on the measured
+  step time), so with the same arguments every run's last step sees the same inputs.
 """
 
 from __future__ import annotations
@@ -263,9 +270,10 @@ def preheat(step, device, dist=None) -> int:
     return n + 3
 
 
-def timed(step, steps, warmup, device, dist=None):
-    """[untimed preheat, see above] + W warm-up + K timed steps bracketed by barrier + synchronize; returns
-    (wall s [max over ranks], device ms)."""
+def timed(step, steps, warmup, device, dist=None, reset=None):
+    """[untimed preheat, see above] + [reset()] + W warm-up + K timed steps bracketed by barrier + synchronize; returns
+    (wall s [max over ranks], device ms).  `reset` rewinds a stateful leg after the preheat, so that the warm-up and
+    timed steps start from the same state whatever number of preheat steps the probe chose."""
     # The cyclic garbage collector stays out of the timed region (as `timeit` does): a generation-2 pass over the
     # objects earlier legs left behind is tens of milliseconds of HOST time that would be charged to K device steps
     # (SBI_AMD_BENCH_KEEP_GC=1 keeps it on, for A/B).  It runs BEFORE the warm-up: nothing that idles the device for
@@ -275,6 +283,8 @@ def timed(step, steps, warmup, device, dist=None):
         gc.collect()
         gc.disable()
     n_pre = preheat(step, device, dist)
+    if reset is not None:
+        reset()
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -305,6 +315,22 @@ def timed(step, steps, warmup, device, dist=None):
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item()), dev_ms
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """`out_dir/<name>.npy` (float32) for every tensor of `arrays`; refuses to write more than 64 MB in all."""
+    import numpy as np
+
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def load_traffic():
@@ -361,15 +387,28 @@ class TrainLeg:
 
         self.sampler = ShuffledGather(theta_all, x_all, None, seed=20260924)
         self.calls = 0
+        self.losses = None
+        self.initial = self.stepper.snapshot()
+
+    def reset(self):
+        """Weights, optimizer state and batch order back to where the leg started (for timed(reset=...))."""
+        self.stepper.restore(self.initial)
+        self.calls = 0
 
     def __call__(self):
         th, xx = self.sampler.batch(self.calls, 0, self.batch)
         self.calls += 1
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        self.stepper.step(th, xx, global_batch=self.global_batch)
+        self.losses = self.stepper.step(th, xx, global_batch=self.global_batch)
         e1.record()
         self.events.append((e0, e1))
+
+    def outputs(self) -> dict:
+        """What a caller of the last step holds: its per-row losses and the updated parameters / optimizer state."""
+        s = self.stepper
+        return {"losses": self.losses, "params": s.net.flat_params.data, "grad": s.grad, "exp_avg": s.exp_avg,
+                "exp_avg_sq": s.exp_avg_sq}
 
     def fused_ms(self, last: int) -> float:
         """Sum of the fused-step device times of the last `last` calls (after the final synchronize)."""
@@ -640,7 +679,18 @@ def main(argv=None):
                     help="train leg without the batch-200 / 8 192 object (traffic passes: bytes per step of the headline)")
     ap.add_argument("--no-rccl-leg", action="store_true",
                     help="N = 1: skip the self-launched 1-rank RCCL run of the train leg (`rccl_1rank` object)")
+    ap.add_argument("--full", action="store_true",
+                    help="default mode: every secondary leg, nested object and CPU baseline besides the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the headline leg's last timed step computed as DIR/<name>.npy (float32)")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.mode not in ("both", "train", "log_prob", "log_prob_broadcast", "sample"):
+        raise SystemExit(f"bench.py: --dump-outputs is not available with --mode {args.mode}")
+    plain = args.mode == "both" and not args.full
+    if plain:
+        # a plain run measures its headline alone: the train leg without its side objects and without CPU baselines
+        args.mode = "train"
+        args.no_cpu_baseline = args.no_small_batch = args.no_rccl_leg = True
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -713,10 +763,11 @@ def main(argv=None):
         broadcast_from_rank0(dist, est.net.flat_params.data)
 
     results = {}
+    last = {}       # leg -> {name: tensor} of its last timed step (--dump-outputs)
     if args.mode in ("both", "log_prob"):
         def lp_step():
             with torch.no_grad():
-                est.log_prob(theta, x)
+                last["log_prob"] = {"log_prob": est.log_prob(theta, x)}
 
         wall, dev_ms = timed(lp_step, args.steps, args.warmup, device, dist)
         results["log_prob"] = {"value": GB * args.steps / wall, "unit": "evals/s",
@@ -729,7 +780,7 @@ def main(argv=None):
 
         def lpb_step():
             with torch.no_grad():
-                est.log_prob(th_s, x_o1)
+                last["log_prob_broadcast_x"] = {"log_prob": est.log_prob(th_s, x_o1)}
 
         wall, dev_ms = timed(lpb_step, args.steps, args.warmup, device, dist)
         results["log_prob_broadcast_x"] = {"value": GB * args.steps / wall, "unit": "evals/s",
@@ -747,10 +798,12 @@ def main(argv=None):
         nd = args.draws
 
         def sample_step():
-            posterior.sample((nd,), x=x_o, max_sampling_batch_size=nd, show_progress_bars=False)
+            last["sample"] = {"samples": posterior.sample((nd,), x=x_o, max_sampling_batch_size=nd,
+                                                          show_progress_bars=False)}
 
         ssteps = max(1, min(args.steps, 10))
-        wall, dev_ms = timed(sample_step, ssteps, min(args.warmup, 2), device, dist)
+        wall, dev_ms = timed(sample_step, ssteps, min(args.warmup, 2), device, dist,
+                             reset=lambda: torch.manual_seed(2))     # the draws do not depend on the preheat's length
         results["sample"] = {"value": nd * world * ssteps / wall, "unit": "draws/s", "steps": ssteps,
                              "ms_per_step": wall / ssteps * 1e3, "roofline": roofline(F_EVAL, nd, ssteps, dev_ms)}
         # M3 with acceptance < 1 (`BoxUniform(-1, 1)`; reference plumbing direct_posterior.py:177-213,
@@ -866,7 +919,9 @@ def main(argv=None):
         n_train = int(0.9 * N_SIMS)
         th_all, x_all = make_data(n_train, device, seed=1000 + (rank if args.scaling == "weak" else 0))
         leg = TrainLeg(est, th_all, x_all, B, distributed, GB)
-        wall, dev_ms = timed(leg, args.steps, args.warmup, device, dist)
+        wall, dev_ms = timed(leg, args.steps, args.warmup, device, dist, reset=leg.reset)
+        if args.dump_outputs:      # copies: the --full legs after this one train the same estimator further
+            last["train"] = {k: v.clone() for k, v in leg.outputs().items()}
         # roofline: the fused step's kernels only (pack, forward, the backward launch over all T transforms, reduce, [all-reduce], clip+Adam),
         # HIP events on the launch stream around every step; the sampler's gather kernel is in `value` only
         fused_ms = leg.fused_ms(args.steps)
@@ -875,7 +930,7 @@ def main(argv=None):
                             "roofline": roofline(F_TRAIN, B, args.steps, fused_ms, "train")}
         results["train"]["roofline"]["whole_step_device_ms"] = dev_ms / args.steps
         results["train"]["host"] = dict(LAST_TIMED)
-        if world > 1 and args.scaling == "weak" and args.batch % world == 0:
+        if world > 1 and args.scaling == "weak" and args.batch % world == 0 and not plain:
             # the same inner loop with the 65 536-pair global batch split over the ranks
             Bs = args.batch // world
             leg_s = TrainLeg(est, th_all, x_all, Bs, distributed, args.batch)
@@ -933,6 +988,12 @@ def main(argv=None):
     if rank == 0:
         head = next(k for k in ("train", "log_prob", "log_prob_broadcast_x", "sample") if k in results)
         r = results[head]
+        if args.dump_outputs:
+            arrays = dict(last[head])
+            if head == "sample":     # 10^6 draws: a fixed, seeded sample of 65 536 of them
+                pick = torch.randperm(args.draws, generator=torch.Generator().manual_seed(0))[:65536].sort().values
+                arrays["samples"] = arrays["samples"][pick.to(arrays["samples"].device)]
+            dump_outputs(args.dump_outputs, arrays)
         per = "per GPU" if args.scaling == "weak" else f"global, {B} per GPU"
         out = {
             "metric": {"train": "NPE train (theta,x)-pairs/sec", "log_prob": "NSF log_prob evals/sec",

@@ -10,9 +10,9 @@ out=$R/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 run() { timeout -k 5 "$@" < /dev/null; }
-# 1. the driver's command (CPU baselines included) and a per-kernel trace of the same legs
-run 400 python $R/bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
-run 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-rccl-leg > $out/trace.log 2>&1
+# 1. the full benchmark line (every leg, CPU baselines included) and a per-kernel trace of the same legs
+run 400 python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench.json 2> $out/bench.err
+run 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-rccl-leg > $out/trace.log 2>&1
 cp $(ls $out/trace/*/*kernel_stats.csv | head -1) $out/kernel_stats.csv
 # 2. counters of the training kernels: one group per pass, no trace domains.  Counter passes COUNT, they do not time:
 #    bench.py's untimed preheat steps are switched off so that launches per run = warm-up + timed steps
