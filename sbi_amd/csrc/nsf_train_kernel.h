@@ -214,7 +214,7 @@ __device__ __forceinline__ void dw_gemm(const float* __restrict__ Ast, const flo
   if (abl & 1) return;
   const float ones_b = id.j == 0 ? 1.f : 0.f;   // B operand of the bias-gradient MFMA: column 0 = sum over the rows
   // few MFMAs per K-step (NT < 4) cover less LDS latency per step: look further ahead
-  constexpr int KS = TR_ROWS / 4, LA = NT >= 4 ? TR_LA : 2 * TR_LA;
+  constexpr int KS = TR_ROWS / 4, LA = NT >= 3 ? TR_LA : 2 * TR_LA;
   // K-step s covers tile rows krow(s) + 4 g (not 4 s + g): with the gradient tiles' row stride 68 (= 4 mod 64,
   // what keeps the ROW waves' accesses conflict-free) the four k-slots of an A read then sit 16 banks apart
   // (4 * 68 = 16 mod 64) instead of 4, so the read is conflict-free as well (it was a 4-way conflict).
@@ -281,6 +281,67 @@ __device__ __forceinline__ void dw_gemm_rs(const float* __restrict__ Ast, const 
     for (int nt = 0; nt < NT; ++nt)   // NT == 1: no guard (a guard per MFMA costs a basic block and an s_waitcnt each)
       if (NT == 1 || nt < nt_on) acc[nt] = MFMA16(a[s % (LA + 1)], b[s % (LA + 1)][nt], acc[nt]);
     __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---- thin remainder of the 50-wide hidden layers (static default layout).  Of m-tile / n-tile 3 (features 48..63) only
+// 48, 49 and the bias column 50 are real, so grad wave 3's hidden d W tiles (rows 48..63) and the other waves' n-tile 3
+// are mostly padding.  In the static instantiation waves 0-2 skip n-tile 3 and wave 3 computes every real entry of the
+// remainder -- the M-strip (rows 48..51 x columns 0..63) and the N-strips (rows 0..47 x columns 48..51) -- on
+// v_mfma_f32_4x4x1_16b_f32: 16 independent 4x4 blocks, lane l supplies A[m = l & 3] and B[n = l & 3] of block l >> 2,
+// D[m][n] of a block sits in lane 4 (l >> 2) + n, register m (tools/ubench/mfma_4x4.hip).
+// Bit-identical to the padded tiles: a 16x16x4 f32 MFMA is a chain of fmas over its k-slots 0..3 in order, a 4x4x1 one
+// fma (profiles/r7_ubench_mfma_4x4.txt), so one 4x4x1 per tile row, rows in dw_gemm's order (krow(s) + 4 g, g inner),
+// repeats every entry's rounding sequence exactly.
+#define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
+constexpr int TR_THIN_C0 = 48;   // first feature of the remainder
+static_assert(kStaticPl.H == TR_THIN_C0 + 2 && kStaticPl.KSH == 13 && kStaticPl.NB == 2,
+              "thin remainder: the static layout's hidden width leaves 2 real features (+ bias column) in tile 3");
+
+// accM: lane l, reg m = d W[48 + m][l];  accN: lane l < 48, reg m = d W[4 (l >> 2) + m][48 + (l & 3)]
+template <int SA, int SB>
+__device__ __forceinline__ void dw_thin(const float* __restrict__ Ast, const float* __restrict__ Bst, const LaneId& id,
+                                        f4& accM, f4& accN) {
+  const int l = id.lane;
+  const float* aM = Ast + TR_THIN_C0 + (l & 3);            // gradient column 48 + m
+  const float* aN = Ast + l;                               // gradient column l (lanes >= 48: discarded rows)
+  const float* bM = Bst + il_col(l);                       // activation column l (interleaved tile)
+  const float* bN = Bst + il_col(TR_THIN_C0 + (l & 3));    // activation column 48 + n
+  constexpr int KS = TR_ROWS / 4;
+  float v[2][4][4];                                        // [buffer][g][aM, bM, aN, bN]
+  auto load = [&](int u, int s) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int r = dw_krow(s) + 4 * g;
+      v[u][g][0] = aM[r * SA];
+      v[u][g][1] = bM[r * SB];
+      v[u][g][2] = aN[r * SA];
+      v[u][g][3] = bN[r * SB];
+    }
+  };
+  load(0, 0);
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    if (s + 1 < KS) load((s + 1) & 1, s + 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      accM = MFMA4(v[s & 1][g][0], v[s & 1][g][1], accM);
+      accN = MFMA4(v[s & 1][g][2], v[s & 1][g][3], accN);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// one hidden d W tile set of a grad wave in the static instantiation (the padded tiles elsewhere)
+template <bool THIN>
+__device__ __forceinline__ void dw_hidden(const float* __restrict__ Ast, const float* __restrict__ Bst, int gw,
+                                          const LaneId& id, f4 (&acc)[4], int abl) {
+  if constexpr (THIN) {
+    if (abl & 1) return;
+    if (gw == TR_NW - 1) dw_thin<TR_SA, TR_SB>(Ast, Bst, id, acc[0], acc[1]);
+    else dw_gemm<3, TR_SA, TR_SB, true>(Ast, Bst, 16 * gw, 0, id, *reinterpret_cast<f4(*)[3]>(&acc[0]));
+  } else {
+    dw_gemm<4, TR_SA, TR_SB, true>(Ast, Bst, 16 * gw, 0, id, acc, 4, abl, nullptr);
   }
 }
 
@@ -650,6 +711,24 @@ __device__ __forceinline__ void write_tile(float* __restrict__ part, const LinDe
     if (out < L.out) {
       if (in < L.in) part[L.g_w + out * L.in + in] = acc[r];
       else if (in == L.in) part[L.g_b + out] = acc[r];
+    }
+  }
+}
+// partial-gradient write-out of grad wave 3's thin strips (see dw_thin)
+__device__ __forceinline__ void write_thin(float* __restrict__ part, const LinDesc& L, const LaneId& id, const f4& accM,
+                                           const f4& accN) {
+  const int l = id.lane;
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    const int outM = TR_THIN_C0 + m, inM = l;
+    if (outM < L.out) {
+      if (inM < L.in) part[L.g_w + outM * L.in + inM] = accM[m];
+      else if (inM == L.in) part[L.g_b + outM] = accM[m];
+    }
+    const int outN = 4 * (l >> 2) + m, inN = TR_THIN_C0 + (l & 3);
+    if (l < TR_THIN_C0 && outN < L.out) {
+      if (inN < L.in) part[L.g_w + outN * L.in + inN] = accN[m];
+      else if (inN == L.in) part[L.g_b + outN] = accN[m];
     }
   }
 }
@@ -1308,7 +1387,8 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
         for (int b = NB - 1; b >= 0; --b) {
           __syncthreads();                         // X1
           TS(21 + 8 * b);
-          dw_gemm<4, TR_SA, TR_SB, true>(lds + o_AY, Bt, 16 * gw, 0, id, acc2[b], 4, NSF_ABLV, HB ? &acc2b[b] : nullptr);
+          if constexpr (SP != 0) dw_hidden<true>(lds + o_AY, Bt, gw, id, acc2[b], NSF_ABLV);
+          else dw_gemm<4, TR_SA, TR_SB, true>(lds + o_AY, Bt, 16 * gw, 0, id, acc2[b], 4, NSF_ABLV, HB ? &acc2b[b] : nullptr);
           TS(22 + 8 * b);
           __syncthreads();                         // X2
           // d Wc under the row waves' re-staging of AY / B (the matrix pipe used to idle between X2 and X3): its
@@ -1316,7 +1396,8 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
           dw_gemm_rs<NTW, TR_SA>(lds + o_AX, Bs, SS, 16 * gw, S.d_id, id, accC[b], ntc, NSF_ABLV);
           __syncthreads();                         // X3
           TS(24 + 8 * b);
-          dw_gemm<4, TR_SA, TR_SB, true>(lds + o_AY, Bt, 16 * gw, 0, id, acc1[b], 4, NSF_ABLV, HB ? &acc1b[b] : nullptr);
+          if constexpr (SP != 0) dw_hidden<true>(lds + o_AY, Bt, gw, id, acc1[b], NSF_ABLV);
+          else dw_gemm<4, TR_SA, TR_SB, true>(lds + o_AY, Bt, 16 * gw, 0, id, acc1[b], 4, NSF_ABLV, HB ? &acc1b[b] : nullptr);
           TS(25 + 8 * b);
           if (b > 0) __syncthreads();              // X4
         }
@@ -1346,10 +1427,15 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
       for (int b = 0; b < NB; ++b) {
   #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) write_tile(part, S.lin[1 + 3 * b], out0, nt, id, accC[b][nt]);
+        if (SP != 0 && gw == TR_NW - 1) {     // the thin strips (static instantiation, see dw_thin)
+          write_thin(part, S.lin[2 + 3 * b], id, acc1[b][0], acc1[b][1]);
+          write_thin(part, S.lin[3 + 3 * b], id, acc2[b][0], acc2[b][1]);
+        } else {
   #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          write_tile(part, S.lin[2 + 3 * b], out0, nt, id, acc1[b][nt]);
-          write_tile(part, S.lin[3 + 3 * b], out0, nt, id, acc2[b][nt]);
+          for (int nt = 0; nt < (SP != 0 ? 3 : 4); ++nt) {   // (static: n-tile 3 is in wave 3's N-strips)
+            write_tile(part, S.lin[2 + 3 * b], out0, nt, id, acc1[b][nt]);
+            write_tile(part, S.lin[3 + 3 * b], out0, nt, id, acc2[b][nt]);
+          }
         }
         if (HB) {
           write_bias(part, S.lin[2 + 3 * b], out0, id, acc1b[b]);
