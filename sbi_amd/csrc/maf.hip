@@ -158,24 +158,20 @@ static int maf_plan_for_rows(const sbi_amd_maf_config* cfg, int64_t n, int cap, 
   return SBI_AMD_E_LDS;
 }
 
-template int maf_dispatch_k<10>(const MafPlan&, int, int, const float*, const float*, const float*, const float*,
-                                int64_t, int64_t, float*, float*, float*, const MafBwdArgs*, hipStream_t);
 #define MAF_EXTERN_K(KK) \
   extern template int maf_dispatch_k<KK>(const MafPlan&, int, int, const float*, const float*, const float*, \
                                          const float*, int64_t, int64_t, float*, float*, float*, const MafBwdArgs*, \
                                          hipStream_t);
-MAF_EXTERN_K(4) MAF_EXTERN_K(5) MAF_EXTERN_K(8) MAF_EXTERN_K(16)
+NSF_FOR_EACH_BINS(MAF_EXTERN_K)   // (every K lives in maf_k<K>.hip but 10, instantiated here)
+template int maf_dispatch_k<10>(const MafPlan&, int, int, const float*, const float*, const float*, const float*,
+                                int64_t, int64_t, float*, float*, float*, const MafBwdArgs*, hipStream_t);
 
 static int maf_dispatch(const MafPlan& mp, int nw, int mode, const float* packed, const float* zstats, const float* in,
                         const float* x, int64_t n, int64_t x_rows, float* out_main, float* out_aux, float* z_stash,
                         const MafBwdArgs* bwd, hipStream_t st) {
-  switch (mp.n.K) {
-#define MAF_CASE(KK) \
-  case KK: return maf_dispatch_k<KK>(mp, nw, mode, packed, zstats, in, x, n, x_rows, out_main, out_aux, z_stash, bwd, st);
-    MAF_CASE(4) MAF_CASE(5) MAF_CASE(8) MAF_CASE(10) MAF_CASE(16)
-#undef MAF_CASE
-    default: return SBI_AMD_E_UNSUPPORTED;
-  }
+  return nsf_with_bins(mp.n.K, [&](auto k) {
+    return maf_dispatch_k<k>(mp, nw, mode, packed, zstats, in, x, n, x_rows, out_main, out_aux, z_stash, bwd, st);
+  });
 }
 
 extern "C" int64_t sbi_amd_maf_param_count(const sbi_amd_maf_config* cfg) {

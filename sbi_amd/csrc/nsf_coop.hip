@@ -8,16 +8,16 @@
 #include "nsf_coop_wide_kernel.h"
 #include "debug_env.h"
 
-template int co_fwd_k<10>(const NsfPlan&, const CoopPlan&, const CoFwdArgs&, hipStream_t);
-template int co_bwd_k<10>(const NsfPlan&, const CoopPlan&, const CoBwdArgs&, hipStream_t);
-template int co_inv_k<10>(const NsfPlan&, const CoopPlan&, const float*, const float*, const float*, const float*,
-                          long long, long long, float*, float*, hipStream_t);
 #define CO_EXTERN(KK)                                                                                       \
   extern template int co_fwd_k<KK>(const NsfPlan&, const CoopPlan&, const CoFwdArgs&, hipStream_t);        \
   extern template int co_bwd_k<KK>(const NsfPlan&, const CoopPlan&, const CoBwdArgs&, hipStream_t);        \
   extern template int co_inv_k<KK>(const NsfPlan&, const CoopPlan&, const float*, const float*, const float*,  \
                                    const float*, long long, long long, float*, float*, hipStream_t);
-CO_EXTERN(4) CO_EXTERN(5) CO_EXTERN(8) CO_EXTERN(16)
+NSF_FOR_EACH_BINS(CO_EXTERN)   // (every K lives in nsf_coop_k<K>.hip but 10, instantiated here)
+template int co_fwd_k<10>(const NsfPlan&, const CoopPlan&, const CoFwdArgs&, hipStream_t);
+template int co_bwd_k<10>(const NsfPlan&, const CoopPlan&, const CoBwdArgs&, hipStream_t);
+template int co_inv_k<10>(const NsfPlan&, const CoopPlan&, const float*, const float*, const float*, const float*,
+                          long long, long long, float*, float*, hipStream_t);
 
 // Does an n-row call take the cooperative kernels?  `training`: the stash-writing forward + backward pair.
 // SBI_AMD_ABLATE bit 16384 switches the path off (A/B measurements, tests of the throughput kernels at small n).
@@ -59,66 +59,64 @@ int coop_pack(const sbi_amd_nsf_config* cfg, const float* params, float* cimg, i
 
 static int co_dispatch_fwd(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPlan& cp, const CoFwdArgs& a,
                            hipStream_t st) {
-  switch (cfg->K) {
-    case 4: return co_fwd_k<4>(pl, cp, a, st);
-    case 5: return co_fwd_k<5>(pl, cp, a, st);
-    case 8: return co_fwd_k<8>(pl, cp, a, st);
-    case 10: return co_fwd_k<10>(pl, cp, a, st);
-    case 16: return co_fwd_k<16>(pl, cp, a, st);
-  }
-  return SBI_AMD_E_UNSUPPORTED;
+  return nsf_with_bins(cfg->K, [&](auto k) { return co_fwd_k<k>(pl, cp, a, st); });
 }
 int coop_sample(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPlan& cp, const float* cimg,
                 const float* zstats, const float* noise, const float* x, int64_t n, int64_t x_rows, float* theta_out,
                 float* logabsdet_out, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  switch (cfg->K) {
-    case 4: return co_inv_k<4>(pl, cp, cimg, zstats, noise, x, n, x_rows, theta_out, logabsdet_out, st);
-    case 5: return co_inv_k<5>(pl, cp, cimg, zstats, noise, x, n, x_rows, theta_out, logabsdet_out, st);
-    case 8: return co_inv_k<8>(pl, cp, cimg, zstats, noise, x, n, x_rows, theta_out, logabsdet_out, st);
-    case 10: return co_inv_k<10>(pl, cp, cimg, zstats, noise, x, n, x_rows, theta_out, logabsdet_out, st);
-    case 16: return co_inv_k<16>(pl, cp, cimg, zstats, noise, x, n, x_rows, theta_out, logabsdet_out, st);
-  }
-  return SBI_AMD_E_UNSUPPORTED;
-}
-
-static int co_dispatch_bwd(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPlan& cp, const CoBwdArgs& a,
-                           hipStream_t st) {
-  switch (cfg->K) {
-    case 4: return co_bwd_k<4>(pl, cp, a, st);
-    case 5: return co_bwd_k<5>(pl, cp, a, st);
-    case 8: return co_bwd_k<8>(pl, cp, a, st);
-    case 10: return co_bwd_k<10>(pl, cp, a, st);
-    case 16: return co_bwd_k<16>(pl, cp, a, st);
-  }
-  return SBI_AMD_E_UNSUPPORTED;
+  return nsf_with_bins(cfg->K, [&](auto k) {
+    return co_inv_k<k>(pl, cp, cimg, zstats, noise, x, n, x_rows, theta_out, logabsdet_out, (hipStream_t)stream);
+  });
 }
 
 // workgroups of nsf_coop_reduce_kernel = partial sums of squares it leaves behind the stash
 static inline int64_t co_sq_parts(const NsfPlan& pl, const CoopPlan& cp) { return (int64_t)((cp.PLP / 4 + 63) / 64) * pl.T; }
-// training workspace of the cooperative path: per-transform input state, z_T, log p, partial slabs, stash
-static int64_t co_ws_layout(const NsfPlan& pl, const CoopPlan& cp, int64_t n, int64_t* o_zst, int64_t* o_noise,
-                            int64_t* o_logp, int64_t* o_part, int64_t* o_ast) {
+// training workspace of the cooperative path (float offsets): per-transform input state, z_T, log p, partial slabs,
+// stash, the reduction's partial sums of squares of the gradient (the clip's norm), the debug timeline
+struct CoWs {
+  int64_t zst, noise, logp, part, ast, sq, dbg, total;
+};
+static CoWs co_ws_layout(const NsfPlan& pl, const CoopPlan& cp, int64_t n) {
+  CoWs w;
   int64_t o = 0;
-  *o_zst = o; o += (int64_t)pl.T * n * pl.D;
-  *o_noise = o; o += n * pl.D;
-  *o_logp = o; o += (n + 3) / 4 * 4;
+  w.zst = o; o += (int64_t)pl.T * n * pl.D;
+  w.noise = o; o += n * pl.D;
+  w.logp = o; o += (n + 3) / 4 * 4;
   o = (o + 3) / 4 * 4;
-  *o_part = o; o += (int64_t)pl.T * cp.grid * cp.PLP;
+  w.part = o; o += (int64_t)pl.T * cp.grid * cp.PLP;
   o = (o + 63) / 64 * 64;
-  *o_ast = o; o += (int64_t)pl.T * ((n + 15) / 16) * cp.slots * 256;
-  o += (co_sq_parts(pl, cp) + 3) / 4 * 4;   // partial sums of squares of the reduced gradient (the clip's norm)
-  o += 1024;   // debug timelines (SBI_AMD_TIMELINE): the last 512 int64 of the workspace
-  return o;
+  w.ast = o; o += (int64_t)pl.T * ((n + 15) / 16) * cp.slots * 256;
+  w.sq = o; o += (co_sq_parts(pl, cp) + 3) / 4 * 4;
+  w.dbg = o; o += 1024;   // debug timeline (SBI_AMD_TIMELINE) of the backward pass: 512 int64
+  w.total = o;
+  return w;
 }
-int64_t coop_workspace_floats(const NsfPlan& pl, const CoopPlan& cp, int64_t n) {
-  int64_t a, b, c, d, e;
-  return co_ws_layout(pl, cp, n, &a, &b, &c, &d, &e);
-}
+int64_t coop_workspace_floats(const NsfPlan& pl, const CoopPlan& cp, int64_t n) { return co_ws_layout(pl, cp, n).total; }
 const float* coop_sqnorm_parts(const NsfPlan& pl, const CoopPlan& cp, int64_t n, const float* workspace, int64_t* n_parts) {
   if (n_parts) *n_parts = co_sq_parts(pl, cp);
-  return workspace + coop_workspace_floats(pl, cp, n) - 1024 - (co_sq_parts(pl, cp) + 3) / 4 * 4;
+  return workspace + co_ws_layout(pl, cp, n).sq;
 }
+
+// debug timeline (SBI_AMD_TIMELINE): the stamps of one warm call (the 21st) of each training half, on stderr
+#ifdef NSF_DEBUG
+static void co_print_timeline(bool bwd, const long long* dbg, int64_t n, int NT, hipStream_t st) {
+  static int printed[2];
+  long long h[256];
+  hipStreamSynchronize(st);
+  hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
+  if (printed[bwd]++ != 20) return;
+  fprintf(stderr, "coop %s timeline (cycles since stamp 0 of wave 0), n = %lld, NT = %d\n", bwd ? "bwd" : "fwd",
+          (long long)n, NT);
+  for (int i = 0; i < 64; ++i) {
+    if (!h[i] && !h[64 + i]) continue;
+    fprintf(stderr, "  stamp %2d:", i);
+    for (int w = 0; w < 4; ++w) fprintf(stderr, " %8lld", h[64 * w + i] ? h[64 * w + i] - h[0] : -1);
+    fprintf(stderr, "\n");
+  }
+}
+#else
+static void co_print_timeline(bool, const long long*, int64_t, int, hipStream_t) {}
+#endif
 
 int coop_log_prob(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPlan& cp, const float* cimg,
                   const float* zstats, const float* theta, const float* x, int64_t n, int64_t x_rows, float* logp,
@@ -161,32 +159,17 @@ extern "C" int sbi_amd_mcmc_slice_run(const sbi_amd_nsf_config* cfg, const float
 int coop_train_forward(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPlan& cp, const float* cimg,
                        const float* zstats, const float* theta, const float* x, int64_t n, int64_t x_rows,
                        float* logp_out, float* workspace, void* stream) {
-  int64_t o_zst, o_noise, o_logp, o_part, o_ast;
-  co_ws_layout(pl, cp, n, &o_zst, &o_noise, &o_logp, &o_part, &o_ast);
-  // debug timeline (SBI_AMD_TIMELINE): the stamps land in the (not yet used) partial-slab region and are printed here
-  long long* dbg = sbi_amd_dbg_timeline() ? (long long*)(workspace + o_part) : nullptr;
+  const CoWs w = co_ws_layout(pl, cp, n);
+  // debug timeline: the forward's stamps land in the (not yet used) partial-slab region
+  long long* dbg = sbi_amd_dbg_timeline() ? (long long*)(workspace + w.part) : nullptr;
   if (dbg) hipMemsetAsync(dbg, 0, 256 * sizeof(long long), (hipStream_t)stream);
-  CoFwdArgs a = {cimg, zstats, theta, x, (long long)n, (long long)x_rows, workspace + o_logp, workspace + o_noise,
-                 workspace + o_zst, workspace + o_ast, dbg};
+  CoFwdArgs a = {cimg, zstats, theta, x, (long long)n, (long long)x_rows, workspace + w.logp, workspace + w.noise,
+                 workspace + w.zst, workspace + w.ast, dbg};
   int rc = co_dispatch_fwd(cfg, pl, cp, a, (hipStream_t)stream);
   if (rc) return rc;
-  if (dbg) {
-    static int printed = 0;
-    long long h[256];
-    hipStreamSynchronize((hipStream_t)stream);
-    hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-    if (printed++ == 20) {      // a warm call
-      fprintf(stderr, "coop fwd timeline (cycles since stamp 0 of wave 0), n = %lld, NT = %d\n", (long long)n, cp.NT);
-      for (int i = 0; i < 64; ++i) {
-        if (!h[i] && !h[64 + i]) continue;
-        fprintf(stderr, "  stamp %2d:", i);
-        for (int w = 0; w < 4; ++w) fprintf(stderr, " %8lld", h[64 * w + i] ? h[64 * w + i] - h[0] : -1);
-        fprintf(stderr, "\n");
-      }
-    }
-  }
+  if (dbg) co_print_timeline(false, dbg, n, cp.NT, (hipStream_t)stream);
   if (logp_out) {
-    hipError_t e = hipMemcpyAsync(logp_out, workspace + o_logp, sizeof(float) * n, hipMemcpyDeviceToDevice,
+    hipError_t e = hipMemcpyAsync(logp_out, workspace + w.logp, sizeof(float) * n, hipMemcpyDeviceToDevice,
                                   (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
   }
@@ -198,34 +181,17 @@ int coop_train_backward(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const 
                         const float* cimg, const float* zstats, const float* x, int64_t n, int64_t x_rows,
                         const float* row_weight, float uniform_weight, float* grad_out, float* grad_theta_out,
                         float* grad_x_out, float* loss_out, float* workspace, void* stream) {
-  int64_t o_zst, o_noise, o_logp, o_part, o_ast;
-  co_ws_layout(pl, cp, n, &o_zst, &o_noise, &o_logp, &o_part, &o_ast);
-  const int64_t ws_total = coop_workspace_floats(pl, cp, n);
-  long long* dbg = sbi_amd_dbg_timeline() ? (long long*)(workspace + ws_total - 1024) : nullptr;
+  const CoWs w = co_ws_layout(pl, cp, n);
+  long long* dbg = sbi_amd_dbg_timeline() ? (long long*)(workspace + w.dbg) : nullptr;
   if (dbg) hipMemsetAsync(dbg, 0, 256 * sizeof(long long), (hipStream_t)stream);
-  CoBwdArgs a = {cimg, zstats, x, (long long)n, (long long)x_rows, row_weight, uniform_weight, workspace + o_noise,
-                 workspace + o_zst, workspace + o_ast, workspace + o_part, grad_theta_out, grad_x_out, dbg};
-  int rc = co_dispatch_bwd(cfg, pl, cp, a, (hipStream_t)stream);
+  CoBwdArgs a = {cimg, zstats, x, (long long)n, (long long)x_rows, row_weight, uniform_weight, workspace + w.noise,
+                 workspace + w.zst, workspace + w.ast, workspace + w.part, grad_theta_out, grad_x_out, dbg};
+  int rc = nsf_with_bins(cfg->K, [&](auto k) { return co_bwd_k<k>(pl, cp, a, (hipStream_t)stream); });
   if (rc) return rc;
-  if (dbg) {
-    static int printed = 0;
-    long long h[256];
-    hipStreamSynchronize((hipStream_t)stream);
-    hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-    if (printed++ == 20) {
-      fprintf(stderr, "coop bwd timeline (cycles since stamp 0 of wave 0), n = %lld, NT = %d\n", (long long)n, cp.NT);
-      for (int i = 0; i < 64; ++i) {
-        if (!h[i] && !h[64 + i]) continue;
-        fprintf(stderr, "  stamp %2d:", i);
-        for (int w = 0; w < 4; ++w) fprintf(stderr, " %8lld", h[64 * w + i] ? h[64 * w + i] - h[0] : -1);
-        fprintf(stderr, "\n");
-      }
-    }
-  }
+  if (dbg) co_print_timeline(true, dbg, n, cp.NT, (hipStream_t)stream);
   hipLaunchKernelGGL(nsf_coop_reduce_kernel, dim3((cp.PLP / 4 + 63) / 64, pl.T), dim3(64 * CO_RED_GROUPS), 0,
-                     (hipStream_t)stream, pl, cp, params, (const float*)(workspace + o_part), grad_out,
-                     (const float*)(workspace + o_logp), loss_out, (long long)n,
-                     workspace + ws_total - 1024 - (co_sq_parts(pl, cp) + 3) / 4 * 4);
+                     (hipStream_t)stream, pl, cp, params, (const float*)(workspace + w.part), grad_out,
+                     (const float*)(workspace + w.logp), loss_out, (long long)n, workspace + w.sq);
   return (int)hipGetLastError();
 }
 

@@ -366,3 +366,19 @@ static int launch_flow_ksh(const NsfPlan& pl, int nw, const float* packed, const
   return launch_flow<K, 16, INV>(pl, nw, packed, zstats, in, x, n, x_rows, out_main, out_aux, z_stash, astash, pstash, st);
 }
 
+
+template <bool INV>
+int dispatch_flow(const sbi_amd_nsf_config* cfg, const float* packed, const float* zstats, const float* in,
+                  const float* x, int64_t n, int64_t x_rows, float* out_main, float* out_aux, float* z_stash,
+                  float* astash, float* pstash, void* stream, bool fp32_bin) {
+  if (n == 0) return 0;
+  if (!cfg || !packed || !zstats || !in || !x || !out_main || n < 0 || x_rows < 1) return SBI_AMD_E_BADARG;
+  NsfPlan pl;
+  int nw = 0;
+  int rc = nsf_plan_for_rows(cfg, n, &pl, &nw, INV);   // (only the sampling direction may take 12-wave workgroups)
+  if (rc) return rc;
+  return nsf_with_bins(cfg->K, [&](auto k) {
+    return launch_flow_ksh<k, INV>(pl, nw, packed, zstats, in, x, n, x_rows, out_main, out_aux, z_stash, astash,
+                                   pstash, (hipStream_t)stream, fp32_bin);
+  });
+}

@@ -5,10 +5,6 @@
 #define NSF_GTRAIN_MAIN_TU
 #include "nsf_gtrain_kernel.h"
 
-int nsf_log_prob_stash(const sbi_amd_nsf_config* cfg, const float* packed, const float* zstats, const float* theta,
-                       const float* x, int64_t n, int64_t x_rows, float* logp_out, float* noise_out,
-                       float* z_stash, float* astash, float* pstash, void* stream, bool fp32_bin);
-
 static int g_round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // plan for n rows: the forward kernel's weight image + this kernel's per-wave scratch; nw = waves per workgroup
@@ -104,8 +100,8 @@ int nsf_g_train_forward(const sbi_amd_nsf_config* cfg, const float* packed, cons
   int rc = g_build_plan(cfg, n, &pl, &gp, &nw);
   if (rc) return rc;
   const GWs w = g_ws_layout(pl, gp, n);
-  rc = nsf_log_prob_stash(cfg, packed, zstats, theta, x, n, x_rows, workspace + w.logp, workspace + w.noise,
-                          workspace + w.stash, workspace + w.ast, nullptr, stream, false);
+  rc = dispatch_flow<false>(cfg, packed, zstats, theta, x, n, x_rows, workspace + w.logp, workspace + w.noise,
+                            workspace + w.stash, workspace + w.ast, nullptr, stream, false);
   if (rc) return rc;
   if (logp_out) {
     hipError_t e = hipMemcpyAsync(logp_out, workspace + w.logp, sizeof(float) * n, hipMemcpyDeviceToDevice,
@@ -123,11 +119,8 @@ const float* nsf_g_logp(const sbi_amd_nsf_config* cfg, int64_t n, const float* w
   return workspace + g_ws_layout(pl, gp, n).logp;
 }
 
-template int nsf_gbwd_launch_k<4>(const NsfPlan&, const GTrainPlan&, int, const GBwdArgs&, hipStream_t);
-template int nsf_gbwd_launch_k<5>(const NsfPlan&, const GTrainPlan&, int, const GBwdArgs&, hipStream_t);
-template int nsf_gbwd_launch_k<8>(const NsfPlan&, const GTrainPlan&, int, const GBwdArgs&, hipStream_t);
-template int nsf_gbwd_launch_k<10>(const NsfPlan&, const GTrainPlan&, int, const GBwdArgs&, hipStream_t);
-template int nsf_gbwd_launch_k<16>(const NsfPlan&, const GTrainPlan&, int, const GBwdArgs&, hipStream_t);
+#define G_INSTANTIATE(KK) template int nsf_gbwd_launch_k<KK>(const NsfPlan&, const GTrainPlan&, int, const GBwdArgs&, hipStream_t);
+NSF_FOR_EACH_BINS(G_INSTANTIATE)
 
 int nsf_g_train_backward(const sbi_amd_nsf_config* cfg, const float* params, const float* packed, const float* zstats,
                          const float* x, int64_t n, int64_t x_rows, const float* row_weight, float uniform_weight,
@@ -158,14 +151,7 @@ int nsf_g_train_backward(const sbi_amd_nsf_config* cfg, const float* params, con
     a.GP = workspace + w.gpl; a.G = workspace + w.gbuf; a.LUG = workspace + w.lug;
     a.ACT = workspace + w.act; a.CIN = workspace + w.cin; a.LUA = workspace + w.lua;
     a.npad = w.npad; a.t = t; a.is_last = (t == T - 1); a.par = par;
-    switch (cfg->K) {
-      case 4: rc = nsf_gbwd_launch_k<4>(pl, gp, nw, a, st); break;
-      case 5: rc = nsf_gbwd_launch_k<5>(pl, gp, nw, a, st); break;
-      case 8: rc = nsf_gbwd_launch_k<8>(pl, gp, nw, a, st); break;
-      case 10: rc = nsf_gbwd_launch_k<10>(pl, gp, nw, a, st); break;
-      case 16: rc = nsf_gbwd_launch_k<16>(pl, gp, nw, a, st); break;
-      default: rc = SBI_AMD_E_UNSUPPORTED;
-    }
+    rc = nsf_with_bins(cfg->K, [&](auto k) { return nsf_gbwd_launch_k<k>(pl, gp, nw, a, st); });
     if (rc) return rc;
     // ---- weight gradients of this transform: every linear (wide inputs in pieces of 64 columns) + LULinear's dU, dL
     MafDwArgs d;

@@ -74,6 +74,13 @@ int nsf_build_plan(const sbi_amd_nsf_config* cfg, int nw, NsfPlan* pl);
 // `wide`: allow 12-wave workgroups (3 per SIMD, one staging buffer per wave) when rows and LDS permit -- measured to
 // pay for the sampling direction only
 int nsf_plan_for_rows(const sbi_amd_nsf_config* cfg, int64_t n, NsfPlan* pl, int* nw_out, bool wide = false);
+// The throughput flow kernel over n rows: INV = false log_prob (in = theta, out_main = log p, out_aux = noise; the
+// training forward also passes the stashes), INV = true sampling (in = noise, out_main = theta, out_aux = logabsdet).
+// Defined in nsf_flow_kernel.h; instantiated in nsf_flow.hip (false) and nsf_flow_inv.hip (true).
+template <bool INV>
+int dispatch_flow(const sbi_amd_nsf_config* cfg, const float* packed, const float* zstats, const float* in,
+                  const float* x, int64_t n, int64_t x_rows, float* out_main, float* out_aux, float* z_stash,
+                  float* astash, float* pstash, void* stream, bool fp32_bin);
 // Packed weight image: T consecutive LDS images (img_floats each), written by
 // nsf_pack_kernel from the flat parameters; kernels stage a layer with a float4 copy.
 // activation-stash slots per (transform, 16-row tile): h_0 | per block t1 t2 sigmoid(gate) h; ctx_mlp: h_1 ... h_{reps+1}

@@ -1,5 +1,6 @@
 // nsf_plan_layout.h -- the integer layout of an NsfPlan as constexpr functions (see nsf_plan.h for what a plan is).
 #pragma once
+#include <type_traits>
 #include "nsf_plan.h"
 
 constexpr int nsf_round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -9,7 +10,24 @@ constexpr int nsf_two_odd_at_least(int v) {   // smallest 2*odd >= v
   return 2 * x;
 }
 
-constexpr int nsf_supported_bins(int K) { return K == 4 || K == 5 || K == 8 || K == 10 || K == 16; }
+// The supported bin counts, written once: X(K) for each.  nsf_supported_bins, nsf_with_bins and the per-K explicit
+// instantiation lists expand it (the kernels of each K are instantiated in a translation unit of their own).
+#define NSF_FOR_EACH_BINS(X) X(4) X(5) X(8) X(10) X(16)
+
+constexpr int nsf_supported_bins(int K) {
+#define NSF_BINS_IS(KK) K == KK ||
+  return NSF_FOR_EACH_BINS(NSF_BINS_IS) false;
+#undef NSF_BINS_IS
+}
+
+// f(std::integral_constant<int, K>{}) for a supported K, SBI_AMD_E_UNSUPPORTED for any other
+template <class F>
+int nsf_with_bins(int K, F&& f) {
+#define NSF_BINS_CALL(KK) if (K == KK) return f(std::integral_constant<int, KK>{});
+  NSF_FOR_EACH_BINS(NSF_BINS_CALL)
+#undef NSF_BINS_CALL
+  return SBI_AMD_E_UNSUPPORTED;
+}
 
 constexpr int nsf_check_cfg(const sbi_amd_nsf_config* c) {
   if (!c) return SBI_AMD_E_BADARG;

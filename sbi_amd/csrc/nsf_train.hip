@@ -102,67 +102,87 @@ static bool fast_path_refuses(int rc) {
   return rc == SBI_AMD_E_UNSUPPORTED || rc == SBI_AMD_E_LDS || (rc == 0 && (sbi_amd_dbg_ablate() & 2048));
 }
 
-int nsf_log_prob_stash(const sbi_amd_nsf_config* cfg, const float* packed, const float* zstats, const float* theta,
-                       const float* x, int64_t n, int64_t x_rows, float* logp_out, float* noise_out,
-                       float* z_stash, float* astash, float* pstash, void* stream, bool fp32_bin);
+// The kernel family of an n-row training pass, with the plans it runs on.  Every entry point of the pass (workspace
+// size, forward, backward, norm parts) takes its decision here, so the two halves always agree on the workspace layout.
+enum { WS_FAM_THROUGHPUT = 0, WS_FAM_COOP = 1, WS_FAM_GENERIC = 2 };
+struct TrainRoute {
+  int fam;
+  NsfPlan pl;         // COOP: the 1-wave plan; THROUGHPUT / GENERIC: the 4-wave plan
+  CoopPlan cp;        // COOP
+  TrainPlan tp;       // THROUGHPUT
+  int refusal;        // GENERIC: why the wave-specialised kernel refused (reported when the generic pass refuses too)
+};
+static int train_route(const sbi_amd_nsf_config* cfg, int64_t n, TrainRoute* r) {
+  if (coop_applies(cfg, n, true, &r->pl, &r->cp)) {
+    r->fam = WS_FAM_COOP;
+    return 0;
+  }
+  // (an E_LDS here speaks about the FORWARD kernel's 4-wave layout; the backward kernel has its own budget, checked
+  // by build_train_plan, and the training forward picks its workgroup size in nsf_plan_for_rows)
+  const int rc = nsf_build_plan(cfg, TR_NW, &r->pl);
+  if (rc && rc != SBI_AMD_E_LDS) return rc;
+  r->refusal = build_train_plan(r->pl, n, &r->tp);
+  if (fast_path_refuses(r->refusal)) {
+    r->fam = WS_FAM_GENERIC;
+    return 0;
+  }
+  if (r->refusal) return r->refusal;
+  r->fam = WS_FAM_THROUGHPUT;
+  return 0;
+}
 
 // workgroups of nsf_grad_reduce_kernel = partial sums of squares it leaves behind the activation stash
 static inline int64_t thr_sq_parts(const NsfPlan& pl, const TrainPlan& tp) { return (int64_t)((tp.PLP / 4 + 63) / 64) * pl.T; }
-static int64_t ws_layout(const NsfPlan& pl, const TrainPlan& tp, int64_t n, int64_t* o_stash, int64_t* o_noise,
-                         int64_t* o_logp, int64_t* o_gza, int64_t* o_gzb, int64_t* o_part, int64_t* o_ast,
-                         int64_t* o_pst = nullptr) {
+// training workspace of the throughput path (float offsets): per-transform input state, z_T, log p, the two dz
+// buffers, partial slabs, activation and spline-parameter stashes, the reduction's partial sums of squares of the
+// gradient (the clip's norm), the debug timeline
+struct ThrWs {
+  int64_t stash, noise, logp, gza, gzb, part, ast, pst, sq, dbg, total;
+};
+static ThrWs thr_ws_layout(const NsfPlan& pl, const TrainPlan& tp, int64_t n) {
+  ThrWs w;
   int64_t o = 0;
-  *o_stash = o; o += (int64_t)pl.T * n * pl.D;
-  *o_noise = o; o += n * pl.D;
-  *o_logp = o; o += (n + 3) / 4 * 4;
-  *o_gza = o; o += n * pl.D;
-  *o_gzb = o; o += n * pl.D;
+  w.stash = o; o += (int64_t)pl.T * n * pl.D;
+  w.noise = o; o += n * pl.D;
+  w.logp = o; o += (n + 3) / 4 * 4;
+  w.gza = o; o += n * pl.D;
+  w.gzb = o; o += n * pl.D;
   o = (o + 3) / 4 * 4;
-  *o_part = o; o += (int64_t)pl.T * tp.grid * tp.PLP;
+  w.part = o; o += (int64_t)pl.T * tp.grid * tp.PLP;
   o = (o + 3) / 4 * 4;
-  *o_ast = o;   // activation stash: T x ceil(n/16) wave-tiles x slots x 1024 floats
+  w.ast = o;   // activation stash: T x ceil(n/16) wave-tiles x slots x 1024 floats
   o += (int64_t)pl.T * ((n + 15) / 16) * nsf_ast_slots(pl) * 1024;
-  if (o_pst) *o_pst = o;   // spline-parameter stash: T x ceil(n/16) wave-tiles x d_tr x PT x 256 floats
+  w.pst = o;   // spline-parameter stash: T x ceil(n/16) wave-tiles x d_tr x PT x 256 floats
   if (TR_PSTASH) o += (int64_t)pl.T * ((n + 15) / 16) * nsf_pst_tile_floats(pl);
-  o += (thr_sq_parts(pl, tp) + 3) / 4 * 4;   // partial sums of squares of the reduced gradient (the clip's norm)
-  o += 2048;   // debug timeline (SBI_AMD_TIMELINE): last 1024 int64 of the workspace
-  return o;
+  w.sq = o; o += (thr_sq_parts(pl, tp) + 3) / 4 * 4;
+  w.dbg = o; o += 2048;   // debug timeline (SBI_AMD_TIMELINE): 1024 int64
+  w.total = o;
+  return w;
 }
 
 extern "C" int64_t sbi_amd_nsf_train_workspace_floats(const sbi_amd_nsf_config* cfg, int64_t n) {
-  {
-    NsfPlan cpl;
-    CoopPlan cp;
-    if (coop_applies(cfg, n > 0 ? n : 1, true, &cpl, &cp)) return coop_workspace_floats(cpl, cp, n > 0 ? n : 1);
-  }
-  NsfPlan pl;
-  // (an E_LDS here speaks about the FORWARD kernel's 4-wave layout; the backward kernel has its own budget, checked
-  // by build_train_plan, and the training forward picks its workgroup size in nsf_plan_for_rows)
-  int rc = nsf_build_plan(cfg, TR_NW, &pl);
-  if (rc && rc != SBI_AMD_E_LDS) return rc;
-  TrainPlan tp;
-  rc = build_train_plan(pl, n > 0 ? n : 1, &tp);
-  if (fast_path_refuses(rc)) {
-    const int64_t g = nsf_g_workspace_floats(cfg, n);
-    return (g >= 0 || g == SBI_AMD_E_LDS) ? g : rc;
-  }
+  TrainRoute r;
+  const int rc = train_route(cfg, n > 0 ? n : 1, &r);
   if (rc) return rc;
-  int64_t a, b, c, d, e, f, g;
-  return ws_layout(pl, tp, n > 0 ? n : 1, &a, &b, &c, &d, &e, &f, &g);
+  switch (r.fam) {
+    case WS_FAM_COOP: return coop_workspace_floats(r.pl, r.cp, n > 0 ? n : 1);
+    case WS_FAM_GENERIC: {
+      const int64_t g = nsf_g_workspace_floats(cfg, n);
+      return (g >= 0 || g == SBI_AMD_E_LDS) ? g : r.refusal;
+    }
+  }
+  return thr_ws_layout(r.pl, r.tp, n > 0 ? n : 1).total;
 }
 
+#define BWD_EXTERN(KK) extern template int launch_bwd_k<KK>(const NsfPlan&, const TrainPlan&, const BwdIo&, hipStream_t);
+NSF_FOR_EACH_BINS(BWD_EXTERN)   // (every K lives in nsf_train_k<K>.hip but 10, instantiated here)
 template int launch_bwd_k<10>(const NsfPlan&, const TrainPlan&, const BwdIo&, hipStream_t);
-extern template int launch_bwd_k<5>(const NsfPlan&, const TrainPlan&, const BwdIo&, hipStream_t);
-extern template int launch_bwd_k<4>(const NsfPlan&, const TrainPlan&, const BwdIo&, hipStream_t);
-extern template int launch_bwd_k<16>(const NsfPlan&, const TrainPlan&, const BwdIo&, hipStream_t);
-extern template int launch_bwd_k<8>(const NsfPlan&, const TrainPlan&, const BwdIo&, hipStream_t);
 
 // Which kernel family laid out a workspace: the two halves of a training pass take the decision independently from
 // (cfg, n) and a process-wide threshold (sbi_amd_nsf_set_coop_max_rows); a backward pass that would read a stash the
 // OTHER family wrote (the threshold moved in between) is refused instead of walking a foreign layout.
 #include <mutex>
 #include <unordered_map>
-enum { WS_FAM_THROUGHPUT = 0, WS_FAM_COOP = 1, WS_FAM_GENERIC = 2 };
 static std::mutex g_ws_mu;
 static std::unordered_map<const void*, std::pair<int, int64_t>> g_ws_family;
 static void ws_family_record(const void* ws, int fam, int64_t n) {
@@ -178,39 +198,24 @@ static bool ws_family_mismatch(const void* ws, int fam, int64_t n) {
 }
 
 // forward half of the training pass: log p of every row + the per-transform state / activation stash
-static int train_forward_impl(const sbi_amd_nsf_config* cfg, const float* packed, const float* zstats,
-                              const float* theta, const float* x, int64_t n, int64_t x_rows, float* logp_out,
-                              float* workspace, void* stream, bool fp32_bin) {
-  if (!cfg || !packed || !zstats || !theta || !x || !workspace || n < 1 || x_rows < 1) return SBI_AMD_E_BADARG;
-  NsfPlan pl;
-  {
-    CoopPlan cp;
-    if (coop_applies(cfg, n, true, &pl, &cp)) {
-      ws_family_record(workspace, WS_FAM_COOP, n);
-      return coop_train_forward(cfg, pl, cp, packed + nsf_packed_floats(pl), zstats, theta, x, n, x_rows, logp_out,
-                                workspace, stream);
-    }
-  }
-  // (an E_LDS here speaks about the FORWARD kernel's 4-wave layout; the backward kernel has its own budget, checked
-  // by build_train_plan, and the training forward picks its workgroup size in nsf_plan_for_rows)
-  int rc = nsf_build_plan(cfg, TR_NW, &pl);
-  if (rc && rc != SBI_AMD_E_LDS) return rc;
-  TrainPlan tp;
-  rc = build_train_plan(pl, n, &tp);
-  if (fast_path_refuses(rc)) {
-    ws_family_record(workspace, WS_FAM_GENERIC, n);
+static int train_forward_impl(const TrainRoute& r, const sbi_amd_nsf_config* cfg, const float* packed,
+                              const float* zstats, const float* theta, const float* x, int64_t n, int64_t x_rows,
+                              float* logp_out, float* workspace, void* stream, bool fp32_bin) {
+  ws_family_record(workspace, r.fam, n);
+  if (r.fam == WS_FAM_COOP)
+    return coop_train_forward(cfg, r.pl, r.cp, packed + nsf_packed_floats(r.pl), zstats, theta, x, n, x_rows, logp_out,
+                              workspace, stream);
+  if (r.fam == WS_FAM_GENERIC) {
     const int rg = nsf_g_train_forward(cfg, packed, zstats, theta, x, n, x_rows, logp_out, workspace, stream);
-    return fast_path_refuses(rg) ? rc : rg;
+    return fast_path_refuses(rg) ? r.refusal : rg;
   }
-  if (rc) return rc;
-  ws_family_record(workspace, WS_FAM_THROUGHPUT, n);
-  int64_t o_stash, o_noise, o_logp, o_gza, o_gzb, o_part, o_ast, o_pst;
-  ws_layout(pl, tp, n, &o_stash, &o_noise, &o_logp, &o_gza, &o_gzb, &o_part, &o_ast, &o_pst);
-  rc = nsf_log_prob_stash(cfg, packed, zstats, theta, x, n, x_rows, workspace + o_logp, workspace + o_noise,
-                          workspace + o_stash, workspace + o_ast, TR_PSTASH ? workspace + o_pst : nullptr, stream, fp32_bin);
+  const ThrWs w = thr_ws_layout(r.pl, r.tp, n);
+  int rc = dispatch_flow<false>(cfg, packed, zstats, theta, x, n, x_rows, workspace + w.logp, workspace + w.noise,
+                                workspace + w.stash, workspace + w.ast, TR_PSTASH ? workspace + w.pst : nullptr, stream,
+                                fp32_bin);
   if (rc) return rc;
   if (logp_out) {
-    hipError_t e = hipMemcpyAsync(logp_out, workspace + o_logp, sizeof(float) * n, hipMemcpyDeviceToDevice,
+    hipError_t e = hipMemcpyAsync(logp_out, workspace + w.logp, sizeof(float) * n, hipMemcpyDeviceToDevice,
                                   (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
   }
@@ -220,90 +225,63 @@ static int train_forward_impl(const sbi_amd_nsf_config* cfg, const float* packed
 extern "C" int sbi_amd_nsf_train_forward(const sbi_amd_nsf_config* cfg, const float* packed, const float* zstats,
                                          const float* theta, const float* x, int64_t n, int64_t x_rows,
                                          float* logp_out, float* workspace, void* stream) {
-  return train_forward_impl(cfg, packed, zstats, theta, x, n, x_rows, logp_out, workspace, stream, false);
+  if (!cfg || !packed || !zstats || !theta || !x || !workspace || n < 1 || x_rows < 1) return SBI_AMD_E_BADARG;
+  TrainRoute r;
+  const int rc = train_route(cfg, n, &r);
+  return rc ? rc : train_forward_impl(r, cfg, packed, zstats, theta, x, n, x_rows, logp_out, workspace, stream, false);
 }
 
 // backward half; loss_out (optional) = -log p of the stash's forward pass, written by the reduction kernel
-static int train_backward_impl(const sbi_amd_nsf_config* cfg, const float* params, const float* packed,
-                               const float* zstats, const float* x, int64_t n, int64_t x_rows,
-                               const float* row_weight, float uniform_weight, float* grad_out,
-                               float* grad_theta_out, float* grad_x_out, float* workspace, float* loss_out,
-                               void* stream) {
-  if (!cfg || !params || !packed || !zstats || !x || !grad_out || !workspace || n < 1 || x_rows < 1)
-    return SBI_AMD_E_BADARG;
-  if (grad_x_out && x_rows != n) return SBI_AMD_E_BADARG;   // one context row per theta row (no reduction here)
-  NsfPlan pl;
-  {
-    // small batches: ONE cooperative backward launch over all transforms, then the same fixed-order slab reduction.
-    // (The workspace was laid out by the cooperative forward: both halves take the same decision from (cfg, n).)
-    CoopPlan cp;
-    if (coop_applies(cfg, n, true, &pl, &cp)) {
-      if (ws_family_mismatch(workspace, WS_FAM_COOP, n)) return SBI_AMD_E_BADARG;
-      return coop_train_backward(cfg, pl, cp, params, packed + nsf_packed_floats(pl), zstats, x, n, x_rows, row_weight,
-                                 uniform_weight, grad_out, grad_theta_out, grad_x_out, loss_out, workspace, stream);
-    }
-  }
-  // (an E_LDS here speaks about the FORWARD kernel's 4-wave layout; the backward kernel has its own budget, checked
-  // by build_train_plan, and the training forward picks its workgroup size in nsf_plan_for_rows)
-  int rc = nsf_build_plan(cfg, TR_NW, &pl);
-  if (rc && rc != SBI_AMD_E_LDS) return rc;
-  TrainPlan tp;
-  rc = build_train_plan(pl, n, &tp);
-  if (ws_family_mismatch(workspace, fast_path_refuses(rc) ? WS_FAM_GENERIC : WS_FAM_THROUGHPUT, n)) return SBI_AMD_E_BADARG;
-  if (fast_path_refuses(rc)) {
-    if (grad_x_out) return rc;   // d loss / d embedded x comes from the wave-specialised kernel only
+static int train_backward_impl(const TrainRoute& r, const sbi_amd_nsf_config* cfg, const float* params,
+                               const float* packed, const float* zstats, const float* x, int64_t n, int64_t x_rows,
+                               const float* row_weight, float uniform_weight, float* grad_out, float* grad_theta_out,
+                               float* grad_x_out, float* workspace, float* loss_out, void* stream) {
+  if (ws_family_mismatch(workspace, r.fam, n)) return SBI_AMD_E_BADARG;
+  if (r.fam == WS_FAM_COOP)   // ONE cooperative backward launch over all transforms, then the fixed-order reduction
+    return coop_train_backward(cfg, r.pl, r.cp, params, packed + nsf_packed_floats(r.pl), zstats, x, n, x_rows,
+                               row_weight, uniform_weight, grad_out, grad_theta_out, grad_x_out, loss_out, workspace,
+                               stream);
+  if (r.fam == WS_FAM_GENERIC) {
+    if (grad_x_out) return r.refusal;   // d loss / d embedded x comes from the wave-specialised kernel only
     if (loss_out) {
       const float* logp = nsf_g_logp(cfg, n, workspace);
-      if (!logp) return rc;
+      if (!logp) return r.refusal;
       hipLaunchKernelGGL(neg_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logp,
                          loss_out, (long long)n);
     }
     const int rg = nsf_g_train_backward(cfg, params, packed, zstats, x, n, x_rows, row_weight, uniform_weight,
                                         grad_out, grad_theta_out, workspace, stream);
-    return fast_path_refuses(rg) ? rc : rg;
+    return fast_path_refuses(rg) ? r.refusal : rg;
   }
-  if (rc) return rc;
+  const NsfPlan& pl = r.pl;
+  TrainPlan tp = r.tp;
   tp.grad_x = grad_x_out;
   hipStream_t st = (hipStream_t)stream;
-  int64_t o_stash, o_noise, o_logp, o_gza, o_gzb, o_part, o_ast, o_pst;
-  const int64_t ws_total = ws_layout(pl, tp, n, &o_stash, &o_noise, &o_logp, &o_gza, &o_gzb, &o_part, &o_ast, &o_pst);
-  float* astash = workspace + o_ast;
-  float* stash = workspace + o_stash;
-  float* noise = workspace + o_noise;
-  float* gz[2] = {workspace + o_gza, workspace + o_gzb};
-  float* partial = workspace + o_part;
-  long long* dbg = (long long*)(workspace + ws_total - 2048);
+  const ThrWs w = thr_ws_layout(pl, tp, n);
   BwdIo io{};
   io.t_hi = pl.T - 1;
   io.t_lo = 0;
   io.packed = packed;
   io.zstats = zstats;
-  io.stash = stash;
+  io.stash = workspace + w.stash;
   io.x = x;
-  io.noise = noise;
-  io.gz[0] = gz[0];
-  io.gz[1] = gz[1];
+  io.noise = workspace + w.noise;
+  io.gz[0] = workspace + w.gza;
+  io.gz[1] = workspace + w.gzb;
   io.row_w = row_weight;
   io.uni_w = uniform_weight;
   io.n = n;
   io.x_rows = x_rows;
-  io.partial = partial;
+  io.partial = workspace + w.part;
   io.grad_theta = grad_theta_out;
-  io.astash = astash;
-  io.pstash = TR_PSTASH ? workspace + o_pst : nullptr;
-  io.dbg = sbi_amd_dbg_timeline() ? dbg : nullptr;
-  switch (cfg->K) {
-    case 4: rc = launch_bwd_k<4>(pl, tp, io, st); break;
-    case 5: rc = launch_bwd_k<5>(pl, tp, io, st); break;
-    case 8: rc = launch_bwd_k<8>(pl, tp, io, st); break;
-    case 10: rc = launch_bwd_k<10>(pl, tp, io, st); break;
-    case 16: rc = launch_bwd_k<16>(pl, tp, io, st); break;
-    default: rc = SBI_AMD_E_UNSUPPORTED;
-  }
+  io.astash = workspace + w.ast;
+  io.pstash = TR_PSTASH ? workspace + w.pst : nullptr;
+  io.dbg = sbi_amd_dbg_timeline() ? (long long*)(workspace + w.dbg) : nullptr;
+  const int rc = nsf_with_bins(cfg->K, [&](auto k) { return launch_bwd_k<k>(pl, tp, io, st); });
   if (rc) return rc;
-  float* sq_out = workspace + ws_total - 2048 - (thr_sq_parts(pl, tp) + 3) / 4 * 4;
   hipLaunchKernelGGL(nsf_grad_reduce_kernel, dim3((tp.PLP / 4 + 63) / 64, pl.T), dim3(64 * RED_GROUPS), 0, st, pl, tp,
-                     params, partial, grad_out, (const float*)(workspace + o_logp), loss_out, (long long)n, sq_out);
+                     params, (const float*)(workspace + w.part), grad_out, (const float*)(workspace + w.logp), loss_out,
+                     (long long)n, workspace + w.sq);
   return (int)hipGetLastError();
 }
 
@@ -313,8 +291,13 @@ extern "C" int sbi_amd_nsf_train_backward(const sbi_amd_nsf_config* cfg, const f
                                           const float* zstats, const float* x, int64_t n, int64_t x_rows,
                                           const float* row_weight, float uniform_weight, float* grad_out,
                                           float* grad_theta_out, float* grad_x_out, float* workspace, void* stream) {
-  return train_backward_impl(cfg, params, packed, zstats, x, n, x_rows, row_weight, uniform_weight, grad_out,
-                             grad_theta_out, grad_x_out, workspace, nullptr, stream);
+  if (!cfg || !params || !packed || !zstats || !x || !grad_out || !workspace || n < 1 || x_rows < 1)
+    return SBI_AMD_E_BADARG;
+  if (grad_x_out && x_rows != n) return SBI_AMD_E_BADARG;   // one context row per theta row (no reduction here)
+  TrainRoute r;
+  const int rc = train_route(cfg, n, &r);
+  return rc ? rc : train_backward_impl(r, cfg, params, packed, zstats, x, n, x_rows, row_weight, uniform_weight,
+                                       grad_out, grad_theta_out, grad_x_out, workspace, nullptr, stream);
 }
 
 // one-call form: forward + backward with weights known up front (plain NPE loss)
@@ -325,10 +308,14 @@ extern "C" int sbi_amd_nsf_loss_fwd_bwd(const sbi_amd_nsf_config* cfg, const flo
                                         float* workspace, void* stream) {
   if (!cfg || !params || !packed || !zstats || !theta || !x || !grad_out || !workspace || n < 1 || x_rows < 1)
     return SBI_AMD_E_BADARG;
-  // (the fused step's forward: its log p is the reported training loss only -- plain fp32 bin, nsf_device.h)
-  int rc = train_forward_impl(cfg, packed, zstats, theta, x, n, x_rows, nullptr, workspace, stream, true);
+  TrainRoute r;
+  int rc = train_route(cfg, n, &r);
   if (rc) return rc;
-  return train_backward_impl(cfg, params, packed, zstats, x, n, x_rows, row_weight, uniform_weight, grad_out,
+  // (the fused step's forward: its log p is the reported training loss only -- plain fp32 bin, nsf_device.h)
+  rc = train_forward_impl(r, cfg, packed, zstats, theta, x, n, x_rows, nullptr, workspace, stream, true);
+  if (rc) return rc;
+  if (grad_x_out && x_rows != n) return SBI_AMD_E_BADARG;
+  return train_backward_impl(r, cfg, params, packed, zstats, x, n, x_rows, row_weight, uniform_weight, grad_out,
                              grad_theta_out, grad_x_out, workspace, loss_out, stream);
 }
 
@@ -339,18 +326,10 @@ extern "C" const float* sbi_amd_nsf_train_sqnorm_parts(const sbi_amd_nsf_config*
                                                        int64_t* n_parts) {
   if (n_parts) *n_parts = 0;
   if (!cfg || !workspace || n < 1) return nullptr;
-  NsfPlan pl;
-  {
-    CoopPlan cp;
-    if (coop_applies(cfg, n, true, &pl, &cp)) return coop_sqnorm_parts(pl, cp, n, workspace, n_parts);
-  }
-  int rc = nsf_build_plan(cfg, TR_NW, &pl);
-  if (rc && rc != SBI_AMD_E_LDS) return nullptr;
-  TrainPlan tp;
-  rc = build_train_plan(pl, n, &tp);
-  if (rc || fast_path_refuses(rc)) return nullptr;
-  int64_t a, b, c, d, e, f, g;
-  const int64_t ws_total = ws_layout(pl, tp, n, &a, &b, &c, &d, &e, &f, &g);
-  if (n_parts) *n_parts = thr_sq_parts(pl, tp);
-  return workspace + ws_total - 2048 - (thr_sq_parts(pl, tp) + 3) / 4 * 4;
+  TrainRoute r;
+  if (train_route(cfg, n, &r)) return nullptr;
+  if (r.fam == WS_FAM_COOP) return coop_sqnorm_parts(r.pl, r.cp, n, workspace, n_parts);
+  if (r.fam == WS_FAM_GENERIC) return nullptr;
+  if (n_parts) *n_parts = thr_sq_parts(r.pl, r.tp);
+  return workspace + thr_ws_layout(r.pl, r.tp, n).sq;
 }

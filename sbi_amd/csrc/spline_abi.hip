@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "nsf_device.h"
+#include "nsf_plan_layout.h"
 #include "../../include/sbi_amd_nsf.h"
 
 struct SplineConst {      // the fields rq_spline_pair reads from its PL argument
@@ -65,13 +66,9 @@ extern "C" int sbi_amd_rq_spline(int32_t num_bins, int32_t inverse, float tail_b
   c.d_const = (float)log(exp(1.0 - (double)min_derivative) - 1.0);
   c.ablate = 0;
   hipStream_t st = (hipStream_t)stream;
-  switch (num_bins) {
-    case 4: launch_spline<4>(inverse != 0, c, params, inputs, n, outputs, logabsdet, st); break;
-    case 5: launch_spline<5>(inverse != 0, c, params, inputs, n, outputs, logabsdet, st); break;
-    case 8: launch_spline<8>(inverse != 0, c, params, inputs, n, outputs, logabsdet, st); break;
-    case 10: launch_spline<10>(inverse != 0, c, params, inputs, n, outputs, logabsdet, st); break;
-    case 16: launch_spline<16>(inverse != 0, c, params, inputs, n, outputs, logabsdet, st); break;
-    default: return SBI_AMD_E_UNSUPPORTED;
-  }
-  return (int)hipGetLastError();
+  const int rc = nsf_with_bins(num_bins, [&](auto k) {
+    launch_spline<k>(inverse != 0, c, params, inputs, n, outputs, logabsdet, st);
+    return 0;
+  });
+  return rc ? rc : (int)hipGetLastError();
 }
