@@ -55,7 +55,12 @@ static bool flow_plan_is_static(const NsfPlan& pl, const NsfPlan& st) {
 // BX: one condition row for the whole launch (x_rows == 1, no training stash): the context-only terms of every
 // transform's conditioner are folded once per workgroup (nsf_device.h, conditioner_hidden<KSH, true>)
 // PREC = false: the spline's bin in plain fp32 (nsf_device.h, rq_spline_pair): the training forward of the static layout
-template <int K, int KSH, bool INV, int SP = 0, bool BX = false, bool PREC = true>
+// TW = 2 (static 8-wave density direction only): each wave owns TWO 16-row tiles, tile16 = wave and nw + wave of the
+// workgroup's 2 nw.  Per transform the image is staged once and the wave runs tile A, then tile B, under it; the tile
+// not running parks its flow state in registers (zs rows: 3 per lane, ld_acc) and swaps it back in with swap_tiles;
+// its context is re-read per transform.  Every row sees the same arithmetic in the same order as with TW = 1
+// (bit-identical results; stash layouts per 16-row tile and per row as before).
+template <int K, int KSH, bool INV, int SP = 0, bool BX = false, bool PREC = true, int TW = 1>
 __global__ void __launch_bounds__(INV ? 768 : 512)
 nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float* __restrict__ zstats,
                 const float* __restrict__ in, const float* __restrict__ x, long long n, long long x_rows,
@@ -68,10 +73,13 @@ nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float
 #define TSF(i) do { } while (0)
 #endif
   constexpr int PT = (3 * K - 1 + 15) / 16;
+  static_assert(TW == 1 || (TW == 2 && SP == 8 && !INV && !BX && kStaticFlow8.C <= 16),
+                "two tiles per wave: static 8-wave density direction with the context in registers only");
   const NsfPlan& pl = SP == 8 ? kStaticFlow8 : (SP == 12 ? kStaticFlow12 : pl_);   // LAYOUT only; floats / debug: pl_
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
-  const int nthreads = blockDim.x;
+  const int nthreads = TW == 2 ? 64 * SP : blockDim.x;   // TW = 2: launched with 64 SP threads only (launch_flow);
+                                                        // the constant folds the staging loops' bounds
   const int wave = tid >> 6;
   const int nw = nthreads >> 6;
   const LaneId id = make_lane();
@@ -83,8 +91,10 @@ nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float
   float* pst = sc + pl.sc_pst;
   float* pst2 = sc + pl.sc_pst2;
 
-  const long long row = (long long)blockIdx.x * (16 * nw) + 16 * wave + id.j;
-  const bool valid = row < n;
+  // the active tile; TW = 2: tile B = tile A + nw, parked while tile A runs and vice versa
+  long long tile16 = (long long)blockIdx.x * (nw * TW) + wave;
+  long long row = (long long)blockIdx.x * (16 * nw * TW) + 16 * wave + id.j;
+  bool valid = row < n;
   const int D = pl.D, C = pl.C;
   const float* th_shift = zstats;
   const float* th_scale = zstats + D;
@@ -108,6 +118,44 @@ nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float
   float* cstd = bxt + 64 * (1 + pl.NB);
   float ld_acc = 0.f;   // per-lane partial of the row's log|det|; reduced over g at the end
   float cr[4] = {0.f, 0.f, 0.f, 0.f};   // standardized context of this lane (C <= 16)
+  // TW = 2: the parked tile's flow state -- zs rows (lane (j, g): dims g, g + 4, g + 8), ld_acc, tile index.  The
+  // context is not parked: cr is recomputed per tile and transform from the raw row xv, which is requested for the tile
+  // that runs next under the LULinear phase of the one running now (cr is live from build_cin on only)
+  constexpr int NZP = TW == 2 ? (kStaticFlow8.D + 3) / 4 : 1;
+  float park_z[NZP], park_ld = 0.f, xv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < NZP; ++k) park_z[k] = 0.f;
+  long long park_tile = tile16 + nw;
+  auto load_ctx = [&](long long tl) {     // xv = what the load + z-score block below reads for tile tl's rows
+    if constexpr (TW == 2) {
+      const long long r = 16 * tl + id.j;
+      const long long xr = (x_rows == n) ? r : (x_rows == 1 ? 0 : r % x_rows);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int c = id.g + 4 * u;
+        xv[u] = (c < C && r < n) ? x[xr * C + c] : 0.f;
+      }
+    }
+  };
+  auto swap_tiles = [&]() {
+    if constexpr (TW == 2) {
+      wave_lds_fence();
+#pragma unroll
+      for (int k = 0; k < NZP; ++k) {
+        const int d = id.g + 4 * k;
+        if (d < D) {
+          const float v = zs[id.j * pl.ZW + d];
+          zs[id.j * pl.ZW + d] = park_z[k];
+          park_z[k] = v;
+        }
+      }
+      wave_lds_fence();
+      { const float v = ld_acc; ld_acc = park_ld; park_ld = v; }
+      { const long long v = tile16; tile16 = park_tile; park_tile = v; }
+      row = 16 * tile16 + id.j;
+      valid = row < n;
+    }
+  };
   if NSF_DBG_ABL(pl_.ablate, 256) {   // test aid (SBI_AMD_ABLATE=256): start from NaN-filled LDS, so that any read of a
     // location the kernel did not write itself shows up in the results
     const int total = pl.lds_w_floats + nw * pl.sc_total;
@@ -116,7 +164,7 @@ nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float
   }
   for (int i = id.lane; i < pl.sc_total; i += 64) sc[i] = 0.f;   // no uninitialised LDS behind short rows
   // ---- load + z-score (PointwiseAffineTransform fwd / Standardize) ----
-  {
+  for (int s = 0; s < TW; ++s) {
     const long long xr = (x_rows == n) ? row : (x_rows == 1 ? 0 : row % x_rows);
     for (int d = id.g; d < D; d += 4) {
       float v = valid ? in[row * D + d] : 0.f;
@@ -140,7 +188,9 @@ nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float
         cs[id.j * pl.CW + c] = (v - x_mean[c]) / x_std[c];
       }
     }
+    swap_tiles();     // TW = 2: tile A loaded and parked, tile B loaded, then A back in (no-op for TW = 1)
   }
+  load_ctx(tile16);
   wave_lds_fence();
 
   auto layer = [&](int li, auto parc) {
@@ -163,118 +213,139 @@ nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float
     TSF(2);
     __syncthreads();
     TSF(3);
-
-    if (!INV && z_stash) {
-      for (int d = id.g; d < D; d += 4)
-        if (valid) z_stash[((long long)t * n + row) * D + d] = zs[id.j * pl.ZW + d];
-    }
-    if (INV && has_lu && !NSF_DBG_ABL(pl_.ablate, 8)) {
-      lu_inverse(lds, pl, S, id, zs, us);
-      if (id.g == 0) ld_acc -= lu_logabsdet(lds, pl, S);
-    }
-    if (BX) build_cin_bx(pl, S, par, id, zs, cin);
-    else build_cin(pl, S, par, id, zs, cs, cr, cin);
-    TSF(4);
-
-    // The two waves of a SIMD run the same phases in lockstep and the arbiter favours the older one, which
-    // then idles at the layer barrier: hand the matrix-heavy hidden phase to the younger wave first and the
-    // spline phase to the older one (measured: sample -3.5 %, log_prob -1 %).
-    if (wave >= (nw >> 1)) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);
-    f4 h[NSF_HT];
-    float* ast = nullptr;
-    if (!INV && astash) {
-      const long long nt16 = (n + 15) / 16;
-      const long long tile16 = (long long)blockIdx.x * nw + wave;
-      if (tile16 < nt16) ast = astash + (((long long)t * nt16 + tile16) * nsf_ast_slots(pl)) * 1024 + 4 * id.lane;
-    }
-    float* pstw = nullptr;      // spline-parameter stash of this wave-tile (training forward only)
-    if (!INV && !BX && pstash) {
-      const long long nt16 = (n + 15) / 16;
-      const long long tile16 = (long long)blockIdx.x * nw + __builtin_amdgcn_readfirstlane(wave);
-      if (tile16 < nt16) pstw = pstash + ((long long)t * nt16 + tile16) * nsf_pst_tile_floats(pl) + 4 * id.lane;
-    }
-    if (!NSF_DBG_ABL(pl_.ablate, 4)) conditioner_hidden<KSH, BX>(lds, pl, S, id, cin + id.j * pl.CINW + id.g, h, ast, bxt);
-    else { for (int mt = 0; mt < NSF_HT; ++mt) for (int r = 0; r < 4; ++r) h[mt][r] = zs[id.j * pl.ZW + (mt + r) % D]; }
-
-    TSF(5);
-    if (wave >= (nw >> 1)) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(2);
-    // ---- final layer + spline, software-pipelined over chunks of DCH dims: the MFMA stream of
-    // chunk c+1 (into the other staging buffer) is issued in the same basic block as the VALU-only
-    // spline of chunk c, so the matrix pipe works under the spline's latency chains.
-    {
-      const int nchunks = (S.d_tr + pl.DCH - 1) / pl.DCH;
-      const int dch_ = pl.DCH, dtr_ = S.d_tr;
-      const bool spl_on = !NSF_DBG_ABL(pl_.ablate, 1);
-      // integer offsets (not a pointer array): keeps the accesses in the LDS address space
-      auto spline_chunk = [&](int c, auto&& yield) {
-        // lane pair (lane, lane^32) = one (row, dim) task; dim slot = bit 4 of the lane id.
-        // Executed by every lane (idle slots recompute a valid task and drop the result) to keep
-        // the block branch-free.
-        const int slot = id.g & 1, part = id.g >> 1;
-        const int dd_raw = c * pl.DCH + slot;
-        const bool live = (slot < dch_) & (dd_raw < dtr_) & spl_on;   // bitwise: no short-circuit branches
-        const int sl = live ? slot : 0;
-        const int dd = live ? dd_raw : c * pl.DCH;
-        const int zi = id.j * pl.ZW + 2 * dd + par;
-        float y, ld;
-        rq_spline_pair_impl<K, INV, 0, PREC>(sc + ((c & 1) ? pl.sc_pst2 : pl.sc_pst) + sl * pl.DS + id.j * pl.PSW, zs[zi], pl_,
-                                             part, y, ld, yield);
-        // every lane stores: partner / idle lanes hold the same y for the same zi (idempotent)
-        zs[zi] = y;
-        ld_acc += (live && part == 0) ? ld : 0.f;
-      };
-      if (pl.sc_pst2 == pl.sc_pst) {
-        // single staging buffer (12-wave workgroups): GEMM of chunk c, then its spline
-        for (int c = 0; c < nchunks; ++c) {
-          int nn = S.d_tr - c * pl.DCH;
-          nn = nn < pl.DCH ? nn : pl.DCH;
-          if (INV && pref_on && c == nchunks - 1 && li + 1 < pl.T)      // sampling direction: next image = transform t - 1
-            stage_issue<NPRE>(packed + (long long)(t - 1) * pl.img_floats, pl.img_floats, tid, nthreads, pre);
-          if (nn == 2) final_layer_chunk_n<PT, KSH, 2>(lds, pst, pl, S, id, h, c * pl.DCH, pstw);
-          else final_layer_chunk_n<PT, KSH, 1>(lds, pst, pl, S, id, h, c * pl.DCH, pstw);
-          wave_lds_fence();
-          spline_chunk(c, NoYield());
-          wave_lds_fence();
-        }
-      } else {
-      {
-        const int n0 = S.d_tr < pl.DCH ? S.d_tr : pl.DCH;
-        if (n0 == 2) final_layer_chunk_n<PT, KSH, 2>(lds, pst, pl, S, id, h, 0, pstw);
-        else final_layer_chunk_n<PT, KSH, 1>(lds, pst, pl, S, id, h, 0, pstw);
+    auto lu_phase = [&]() {
+      if (!INV && has_lu && !NSF_DBG_ABL(pl_.ablate, 8)) {
+        lu_forward(lds, pl, S, id, zs, us);
+        if (id.g == 0) ld_acc += lu_logabsdet(lds, pl, S);
       }
-      wave_lds_fence();
-      for (int c = 0; c < nchunks; ++c) {
-        TSF(6 + 2 * c);
-        const int dnext = (c + 1) * pl.DCH;
-        int nnext = S.d_tr - dnext;
-        nnext = nnext < 0 ? 0 : (nnext < pl.DCH ? nnext : pl.DCH);
-        float* pnext = sc + (((c + 1) & 1) ? pl.sc_pst2 : pl.sc_pst);
-        if (nnext == 2) {
-          // the next chunk's final-layer GEMM advances one MFMA per yield point of this chunk's spline
-          FinalLayerStream<PT, KSH, 2> fs;
-          fs.init(lds, pl, S, id, h, dnext);
-          spline_chunk(c, fs);
-          fs.template finish<5 * K + 1>(pnext, pl, id, pstw, dnext);
-        } else if (nnext == 1) {
-          FinalLayerStream<PT, KSH, 1> fs;
-          fs.init(lds, pl, S, id, h, dnext);
-          spline_chunk(c, fs);
-          fs.template finish<5 * K + 1>(pnext, pl, id, pstw, dnext);
+    };
+    // TW = 2: tile A, then tile B under the same image.  Only the LAST tile's LULinear phase sits outside the loop,
+    // under the next image's stage_issue: pre[] is not touched inside the loop, so it is not live across it.
+    for (int s = 0; s < TW; ++s) {
+      if (s > 0) {      // TW = 2: tile A's LULinear, then tile B in (the context of tile B requested first)
+        load_ctx(park_tile);
+        lu_phase();
+        TSF(21);
+        swap_tiles();
+      }
+      if (!INV && z_stash) {
+        for (int d = id.g; d < D; d += 4)
+          if (valid) z_stash[((long long)t * n + row) * D + d] = zs[id.j * pl.ZW + d];
+      }
+      if (INV && has_lu && !NSF_DBG_ABL(pl_.ablate, 8)) {
+        lu_inverse(lds, pl, S, id, zs, us);
+        if (id.g == 0) ld_acc -= lu_logabsdet(lds, pl, S);
+      }
+      if constexpr (TW == 2) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int c = id.g + 4 * u;
+          cr[u] = (c < C) ? (xv[u] - x_mean[c]) / x_std[c] : 0.f;
+        }
+      }
+      if (BX) build_cin_bx(pl, S, par, id, zs, cin);
+      else build_cin(pl, S, par, id, zs, cs, cr, cin);
+      TSF(4);
+
+      // The two waves of a SIMD run the same phases in lockstep and the arbiter favours the older one, which
+      // then idles at the layer barrier: hand the matrix-heavy hidden phase to the younger wave first and the
+      // spline phase to the older one (measured: sample -3.5 %, log_prob -1 %).
+      if (wave >= (nw >> 1)) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);
+      f4 h[NSF_HT];
+      float* ast = nullptr;
+      if (!INV && astash) {
+        const long long nt16 = (n + 15) / 16;
+        const long long tl = TW == 1 ? (long long)blockIdx.x * nw + wave : tile16;
+        if (tl < nt16) ast = astash + (((long long)t * nt16 + tl) * nsf_ast_slots(pl)) * 1024 + 4 * id.lane;
+      }
+      float* pstw = nullptr;      // spline-parameter stash of this wave-tile (training forward only)
+      if (!INV && !BX && pstash) {
+        const long long nt16 = (n + 15) / 16;
+        const long long tl = TW == 1 ? (long long)blockIdx.x * nw + __builtin_amdgcn_readfirstlane(wave) : tile16;
+        if (tl < nt16) pstw = pstash + ((long long)t * nt16 + tl) * nsf_pst_tile_floats(pl) + 4 * id.lane;
+      }
+      if (!NSF_DBG_ABL(pl_.ablate, 4)) conditioner_hidden<KSH, BX>(lds, pl, S, id, cin + id.j * pl.CINW + id.g, h, ast, bxt);
+      else { for (int mt = 0; mt < NSF_HT; ++mt) for (int r = 0; r < 4; ++r) h[mt][r] = zs[id.j * pl.ZW + (mt + r) % D]; }
+
+      TSF(5);
+      if (wave >= (nw >> 1)) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(2);
+      // ---- final layer + spline, software-pipelined over chunks of DCH dims: the MFMA stream of
+      // chunk c+1 (into the other staging buffer) is issued in the same basic block as the VALU-only
+      // spline of chunk c, so the matrix pipe works under the spline's latency chains.
+      {
+        const int nchunks = (S.d_tr + pl.DCH - 1) / pl.DCH;
+        const int dch_ = pl.DCH, dtr_ = S.d_tr;
+        const bool spl_on = !NSF_DBG_ABL(pl_.ablate, 1);
+        // integer offsets (not a pointer array): keeps the accesses in the LDS address space
+        auto spline_chunk = [&](int c, auto&& yield) {
+          // lane pair (lane, lane^32) = one (row, dim) task; dim slot = bit 4 of the lane id.
+          // Executed by every lane (idle slots recompute a valid task and drop the result) to keep
+          // the block branch-free.
+          const int slot = id.g & 1, part = id.g >> 1;
+          const int dd_raw = c * pl.DCH + slot;
+          const bool live = (slot < dch_) & (dd_raw < dtr_) & spl_on;   // bitwise: no short-circuit branches
+          const int sl = live ? slot : 0;
+          const int dd = live ? dd_raw : c * pl.DCH;
+          const int zi = id.j * pl.ZW + 2 * dd + par;
+          float y, ld;
+          rq_spline_pair_impl<K, INV, 0, PREC>(sc + ((c & 1) ? pl.sc_pst2 : pl.sc_pst) + sl * pl.DS + id.j * pl.PSW, zs[zi], pl_,
+                                               part, y, ld, yield);
+          // every lane stores: partner / idle lanes hold the same y for the same zi (idempotent)
+          zs[zi] = y;
+          ld_acc += (live && part == 0) ? ld : 0.f;
+        };
+        if (pl.sc_pst2 == pl.sc_pst) {
+          // single staging buffer (12-wave workgroups): GEMM of chunk c, then its spline
+          for (int c = 0; c < nchunks; ++c) {
+            int nn = S.d_tr - c * pl.DCH;
+            nn = nn < pl.DCH ? nn : pl.DCH;
+            if (INV && pref_on && c == nchunks - 1 && li + 1 < pl.T)      // sampling direction: next image = transform t - 1
+              stage_issue<NPRE>(packed + (long long)(t - 1) * pl.img_floats, pl.img_floats, tid, nthreads, pre);
+            if (nn == 2) final_layer_chunk_n<PT, KSH, 2>(lds, pst, pl, S, id, h, c * pl.DCH, pstw);
+            else final_layer_chunk_n<PT, KSH, 1>(lds, pst, pl, S, id, h, c * pl.DCH, pstw);
+            wave_lds_fence();
+            spline_chunk(c, NoYield());
+            wave_lds_fence();
+          }
         } else {
-          spline_chunk(c, NoYield());
+        {
+          const int n0 = S.d_tr < pl.DCH ? S.d_tr : pl.DCH;
+          if (n0 == 2) final_layer_chunk_n<PT, KSH, 2>(lds, pst, pl, S, id, h, 0, pstw);
+          else final_layer_chunk_n<PT, KSH, 1>(lds, pst, pl, S, id, h, 0, pstw);
         }
         wave_lds_fence();
+        for (int c = 0; c < nchunks; ++c) {
+          TSF(6 + 2 * c);
+          const int dnext = (c + 1) * pl.DCH;
+          int nnext = S.d_tr - dnext;
+          nnext = nnext < 0 ? 0 : (nnext < pl.DCH ? nnext : pl.DCH);
+          float* pnext = sc + (((c + 1) & 1) ? pl.sc_pst2 : pl.sc_pst);
+          if (nnext == 2) {
+            // the next chunk's final-layer GEMM advances one MFMA per yield point of this chunk's spline
+            FinalLayerStream<PT, KSH, 2> fs;
+            fs.init(lds, pl, S, id, h, dnext);
+            spline_chunk(c, fs);
+            fs.template finish<5 * K + 1>(pnext, pl, id, pstw, dnext);
+          } else if (nnext == 1) {
+            FinalLayerStream<PT, KSH, 1> fs;
+            fs.init(lds, pl, S, id, h, dnext);
+            spline_chunk(c, fs);
+            fs.template finish<5 * K + 1>(pnext, pl, id, pstw, dnext);
+          } else {
+            spline_chunk(c, NoYield());
+          }
+          wave_lds_fence();
+        }
+        }
       }
-      }
+      TSF(20);
     }
-    TSF(20);
     if (!INV && pref_on && li + 1 < pl.T)      // the NEXT transform's image: in flight under LULinear and the wait at the barrier
       stage_issue<NPRE>(packed + (long long)(t + 1) * pl.img_floats, pl.img_floats, tid, nthreads, pre);
-    if (!INV && has_lu && !NSF_DBG_ABL(pl_.ablate, 8)) {
-      lu_forward(lds, pl, S, id, zs, us);
-      if (id.g == 0) ld_acc += lu_logabsdet(lds, pl, S);
-    }
+    if (li + 1 < pl.T) load_ctx(park_tile);   // TW = 2: tile A's context for the next transform
+    lu_phase();
     TSF(21);
+    swap_tiles();     // TW = 2: tile A back in
   };
   if constexpr (SP != 0) {     // parity known at compile time: the transform loop runs in pairs
     constexpr int T_ = (SP == 8 ? kStaticFlow8 : kStaticFlow12).T;
@@ -292,16 +363,19 @@ nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float
 
   // ---- epilogue ----
   if (!INV) {
-    float part = 0.f;
-    for (int d = id.g; d < D; d += 4) {
-      float z = zs[id.j * pl.ZW + d];
-      part += z * z;
-      if (out_aux && valid && !dbg) out_aux[row * D + d] = z;
+    for (int s = 0; s < TW; ++s) {
+      float part = 0.f;
+      for (int d = id.g; d < D; d += 4) {
+        float z = zs[id.j * pl.ZW + d];
+        part += z * z;
+        if (out_aux && valid && !dbg) out_aux[row * D + d] = z;
+      }
+      float v = -0.5f * part + ld_acc;
+      v += __shfl_xor(v, 16);
+      v += __shfl_xor(v, 32);
+      if (id.g == 0 && valid) out_main[row] = v - pl_.log_z;
+      if (s + 1 < TW) swap_tiles();
     }
-    float v = -0.5f * part + ld_acc;
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    if (id.g == 0 && valid) out_main[row] = v - pl_.log_z;
   } else {
     for (int d = id.g; d < D; d += 4) {
       float z = zs[id.j * pl.ZW + d];
@@ -325,7 +399,16 @@ static inline bool nsf_bx_applies(const NsfPlan& pl, int nw, int64_t x_rows, con
          nsf_lds_bytes(pl, nw) + nsf_bx_extra_bytes(pl) <= NSF_LDS_LIMIT_BYTES;
 }
 
-template <int K, int KSH, bool INV, int SP = 0, bool BX = false, bool PREC = true>
+// two 16-row tiles per wave (nsf_flow_kernel, TW = 2) for an n-row call of nw-wave workgroups: a round of 256 such
+// workgroups takes about twice as long as one of single-tile workgroups, so the shape is taken only where it halves the
+// rounds (65 536 rows: one round of 256 instead of two of 256)
+static inline bool nsf_flow_two_tiles(int64_t n, int nw) {
+  const int64_t r1 = ((n + 16 * nw - 1) / (16 * nw) + 255) / 256;
+  const int64_t r2 = ((n + 32 * nw - 1) / (32 * nw) + 255) / 256;
+  return 2 * r2 <= r1;
+}
+
+template <int K, int KSH, bool INV, int SP = 0, bool BX = false, bool PREC = true, int TW = 1>
 static int launch_flow(const NsfPlan& pl, int nw, const float* packed, const float* zstats, const float* in,
                        const float* x, int64_t n, int64_t x_rows, float* out_main, float* out_aux,
                        float* z_stash, float* astash, float* pstash, hipStream_t stream) {
@@ -335,10 +418,10 @@ static int launch_flow(const NsfPlan& pl, int nw, const float* packed, const flo
                                                 astash, pstash, stream);
   }
   const int64_t lds_bytes = nsf_lds_bytes(pl, nw) + (BX ? nsf_bx_extra_bytes(pl) : 0);
-  auto kern = nsf_flow_kernel<K, KSH, INV, SP, BX, PREC>;
+  auto kern = nsf_flow_kernel<K, KSH, INV, SP, BX, PREC, TW>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (e != hipSuccess) return (int)e;
-  const int64_t rows_per_wg = 16 * nw;
+  const int64_t rows_per_wg = 16 * nw * TW;
   const int64_t grid = (n + rows_per_wg - 1) / rows_per_wg;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * nw), (size_t)lds_bytes, stream, pl, packed, zstats, in,
                      x, (long long)n, (long long)x_rows, out_main, out_aux, z_stash, astash, pstash,
@@ -352,8 +435,11 @@ static int launch_flow_ksh(const NsfPlan& pl, int nw, const float* packed, const
                            float* z_stash, float* astash, float* pstash, hipStream_t st, bool fp32_bin = false) {
   if constexpr (K == 10) {     // the benchmark configuration: layout folded into the kernel
     if constexpr (!INV) {
-      if (nw == 8 && flow_plan_is_static(pl, kStaticFlow8) && NSF_TRAIN_FWD_FP32_BIN && fp32_bin && astash)
+      if (nw == 8 && flow_plan_is_static(pl, kStaticFlow8) && NSF_TRAIN_FWD_FP32_BIN && fp32_bin && astash) {
+        if (nsf_flow_two_tiles(n, nw) && !NSF_DBG_ABL(pl.ablate, 0x100000))   // bit 0x100000: one tile per wave
+          return launch_flow<10, 13, INV, 8, false, false, 2>(pl, nw, packed, zstats, in, x, n, x_rows, out_main, out_aux, z_stash, astash, pstash, st);
         return launch_flow<10, 13, INV, 8, false, false>(pl, nw, packed, zstats, in, x, n, x_rows, out_main, out_aux, z_stash, astash, pstash, st);
+      }
       if (nw == 8 && flow_plan_is_static(pl, kStaticFlow8))
         return launch_flow<10, 13, INV, 8>(pl, nw, packed, zstats, in, x, n, x_rows, out_main, out_aux, z_stash, astash, pstash, st);
     } else {
