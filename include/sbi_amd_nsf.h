@@ -114,6 +114,20 @@ int sbi_amd_nsf_log_prob(const sbi_amd_nsf_config* cfg, const float* packed, con
                          const float* theta, const float* x, int64_t n, int64_t x_rows,
                          float* logp_out, float* noise_out, void* stream);
 
+/* NLE's potential over iid trials: loglik_out[c] = sum_i log q(x_i | theta_c) for the estimator q(x | theta) (cfg is
+ * the estimator's own: D is the x dimension, C the theta dimension).  Replaces _log_likelihoods_over_trials
+ * (sbi/inference/potentials/likelihood_based_potential.py:186-236) without building the (trial, theta) pairs: row
+ * r = c * num_trials + i (theta-major) reads x_trials[i] (num_trials, D) and theta[c] (num_theta, C) in place.
+ * row_logp_out (num_trials * num_theta, optional): the per-row values, bit-identical to sbi_amd_nsf_log_prob on the
+ * materialised pairs in the same order (same kernel family and routing for the same row count).  The sum over a
+ * theta's trials is taken in a fixed order that depends on the trial index alone: repeated calls are bit-identical and
+ * permuting the theta rows permutes loglik_out bit for bit.  workspace: ..._workspace_floats floats (unused, may be
+ * NULL, when row_logp_out is given).  Hidden 65 ... 128 (the wide kernels): SBI_AMD_E_UNSUPPORTED. */
+int64_t sbi_amd_nsf_log_prob_trials_workspace_floats(const sbi_amd_nsf_config* cfg, int64_t num_trials, int64_t num_theta);
+int sbi_amd_nsf_log_prob_trials(const sbi_amd_nsf_config* cfg, const float* packed, const float* zstats,
+                                const float* x_trials, int64_t num_trials, const float* theta, int64_t num_theta,
+                                float* loglik_out, float* row_logp_out, float* workspace, void* stream);
+
 /* theta = transform^{-1}(noise | x) for n rows: the arithmetic of
  * Flow._sample behind NFlowsFlow.sample (nflows_flow.py:111-128) for GIVEN
  * base noise (the caller draws it with torch's generator, see DESIGN.md RNG).
@@ -324,7 +338,7 @@ int sbi_amd_rq_spline(int32_t num_bins, int32_t inverse, float tail_bound, float
 int sbi_amd_nsf_coop_selfcheck(const sbi_amd_nsf_config* cfg);
 
 /* Library/ABI version (major*100 + minor) and the gfx arch string it was built for. */
-#define SBI_AMD_NSF_ABI_VERSION 114
+#define SBI_AMD_NSF_ABI_VERSION 115
 int sbi_amd_nsf_abi_version(void);
 const char* sbi_amd_nsf_arch(void);
 

@@ -10,11 +10,13 @@
 
 #define CO_EXTERN(KK)                                                                                       \
   extern template int co_fwd_k<KK>(const NsfPlan&, const CoopPlan&, const CoFwdArgs&, hipStream_t);        \
+  extern template int co_fwd_k<KK, true>(const NsfPlan&, const CoopPlan&, const CoFwdArgs&, hipStream_t);  \
   extern template int co_bwd_k<KK>(const NsfPlan&, const CoopPlan&, const CoBwdArgs&, hipStream_t);        \
   extern template int co_inv_k<KK>(const NsfPlan&, const CoopPlan&, const float*, const float*, const float*,  \
                                    const float*, long long, long long, float*, float*, hipStream_t);
 NSF_FOR_EACH_BINS(CO_EXTERN)   // (every K lives in nsf_coop_k<K>.hip but 10, instantiated here)
 template int co_fwd_k<10>(const NsfPlan&, const CoopPlan&, const CoFwdArgs&, hipStream_t);
+template int co_fwd_k<10, true>(const NsfPlan&, const CoopPlan&, const CoFwdArgs&, hipStream_t);
 template int co_bwd_k<10>(const NsfPlan&, const CoopPlan&, const CoBwdArgs&, hipStream_t);
 template int co_inv_k<10>(const NsfPlan&, const CoopPlan&, const float*, const float*, const float*, const float*,
                           long long, long long, float*, float*, hipStream_t);
@@ -123,6 +125,15 @@ int coop_log_prob(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPl
                   float* noise, void* stream) {
   CoFwdArgs a = {cimg, zstats, theta, x, (long long)n, (long long)x_rows, logp, noise, nullptr, nullptr, nullptr};
   return co_dispatch_fwd(cfg, pl, cp, a, (hipStream_t)stream);
+}
+
+// iid trials (sbi_amd_nsf_log_prob_trials): row r = condition r / num_trials, input r % num_trials; per-row values to logp
+int coop_log_prob_trials(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPlan& cp, const float* cimg,
+                         const float* zstats, const float* x_trials, int64_t num_trials, const float* theta, int64_t n,
+                         float* logp, void* stream) {
+  CoFwdArgs a = {cimg, zstats, x_trials, theta, (long long)n, (long long)num_trials, logp, nullptr, nullptr, nullptr,
+                 nullptr};
+  return nsf_with_bins(cfg->K, [&](auto k) { return co_fwd_k<k, true>(pl, cp, a, (hipStream_t)stream); });
 }
 
 // `nticks` ticks of the vectorised slice sampler for all chains in ONE launch (nsf_coop_kernel.h, MC = true).

@@ -12,6 +12,9 @@ const float* coop_sqnorm_parts(const NsfPlan& pl, const CoopPlan& cp, int64_t n,
 int coop_log_prob(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPlan& cp, const float* cimg,
                   const float* zstats, const float* theta, const float* x, int64_t n, int64_t x_rows, float* logp,
                   float* noise, void* stream);
+int coop_log_prob_trials(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPlan& cp, const float* cimg,
+                         const float* zstats, const float* x_trials, int64_t num_trials, const float* theta, int64_t n,
+                         float* logp, void* stream);
 int coop_sample(const sbi_amd_nsf_config* cfg, const NsfPlan& pl, const CoopPlan& cp, const float* cimg,
                 const float* zstats, const float* noise, const float* x, int64_t n, int64_t x_rows, float* theta_out,
                 float* logabsdet_out, void* stream);

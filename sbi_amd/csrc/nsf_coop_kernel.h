@@ -389,13 +389,16 @@ struct McArgs {
   float *x, *next_param, *width, *fstate, *samples, *theta_next, *lad_next, *logp_buf;
   int *order, *istate, *done_count;
 };
-template <int K, int KSH, int NT, bool LEAN, bool MC = false>
+// TRI: iid trials against a batch of conditions (sbi_amd_nsf_log_prob_trials): x_rows is the number of trials, row r
+// takes condition r / x_rows and input r % x_rows; every row sees the arithmetic of the paired call at the same row count
+template <int K, int KSH, int NT, bool LEAN, bool MC = false, bool TRI = false>
 __global__ void __launch_bounds__(64 * CO_WAVES, LEAN ? 2 : 1)
 nsf_coop_fwd_kernel(const CoK k, const float* __restrict__ cimg, const float* __restrict__ zstats,
                     const float* __restrict__ theta, const float* __restrict__ x, long long n, long long x_rows,
                     float* __restrict__ logp, float* __restrict__ noise_out, float* __restrict__ zst,
                     float* __restrict__ ast, long long* __restrict__ dbg, const McArgs mc) {
   static_assert(!MC || (NT == 1 && !LEAN), "the persistent sampler runs one-tile workgroups");
+  static_assert(!(MC && TRI), "the persistent sampler evaluates one x_o");
   // debug timeline (SBI_AMD_TIMELINE): cycle stamps of workgroup 0's waves while they walk transform 1
 #ifdef NSF_DEBUG
 #define TSC(i) do { if (dbg && blockIdx.x == 0 && (threadIdx.x & 63) == 0 && t == 1) \
@@ -439,7 +442,7 @@ nsf_coop_fwd_kernel(const CoK k, const float* __restrict__ cimg, const float* __
   for (int u = 0; u < NT; ++u) {
     const long long row = row0 + 16 * u + id.j;
     const long long rs = row < n ? row : 0;
-    const long long xr = (x_rows == n) ? rs : (x_rows == 1 ? 0 : rs % x_rows);
+    const long long xr = TRI ? rs / x_rows : ((x_rows == n) ? rs : (x_rows == 1 ? 0 : rs % x_rows));
     float xv[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -465,7 +468,8 @@ nsf_coop_fwd_kernel(const CoK k, const float* __restrict__ cimg, const float* __
   for (int i = tid; i < R * D; i += 64 * CO_WAVES) {
     const int r = i / D, d = i - r * D;
     const long long row = row0 + r;
-    const float th = (MC && tick > 0) ? mc_theta[r * 16 + d] : (row < n ? theta[row * D + d] : 0.f);
+    const long long ir = TRI ? row % x_rows : row;      // TRI: the trial this row evaluates
+    const float th = (MC && tick > 0) ? mc_theta[r * 16 + d] : (row < n ? theta[ir * D + d] : 0.f);
     zs[r * ZS + d] = row < n ? th * th_scale[d] + th_shift[d] : 0.f;
   }
 #pragma unroll
@@ -1286,9 +1290,9 @@ struct CoBwdArgs {
   long long* dbg;
 };
 
-template <int K, int KSH, int NT, bool LEAN, bool MC = false>
+template <int K, int KSH, int NT, bool LEAN, bool MC = false, bool TRI = false>
 static int co_launch_fwd(const CoK& k, const CoopPlan& cp, const CoFwdArgs& a, hipStream_t st) {
-  auto kern = nsf_coop_fwd_kernel<K, KSH, NT, LEAN, MC>;
+  auto kern = nsf_coop_fwd_kernel<K, KSH, NT, LEAN, MC, TRI>;
   const int lds_bytes = 4 * cp.lds_floats;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
   if (e != hipSuccess) return (int)e;

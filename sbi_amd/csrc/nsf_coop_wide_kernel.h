@@ -751,10 +751,12 @@ static int cow_launch_bwd(const CoK& k, const CoopPlan& cp, const CoBwdArgs& a, 
 
 // ------------------------------------------------------------------------------------------------ dispatch
 // one translation unit per bin count (parallel build): nsf_coop.hip holds K = 10, nsf_coop_k{4,5,8,16}.hip the rest
-template <int K>
+// TRI: iid trials (a.x_rows = trials, sbi_amd_nsf_log_prob_trials): the narrow kernels only, same routes as log_prob
+template <int K, bool TRI = false>
 int co_fwd_k(const NsfPlan& pl, const CoopPlan& cp, const CoFwdArgs& a, hipStream_t st) {
   CoK k;
-  if (a.mc) {      // persistent slice sampler: one-tile workgroups (16 chains each), whatever the chain count
+  if (TRI && (a.mc || cp.MT == 2)) return SBI_AMD_E_UNSUPPORTED;
+  if constexpr (!TRI) if (a.mc) {      // persistent slice sampler: one-tile workgroups (16 chains each), whatever the chain count
     if (cp.MT == 2) return SBI_AMD_E_UNSUPPORTED;
     CoopPlan cf = cp;
     if (cp.NT != 1) {
@@ -764,7 +766,7 @@ int co_fwd_k(const NsfPlan& pl, const CoopPlan& cp, const CoFwdArgs& a, hipStrea
     coop_make_consts(pl, cf, &k);
     return pl.KSH == 13 ? co_launch_fwd<K, 13, 1, false, true>(k, cf, a, st) : co_launch_fwd<K, 16, 1, false, true>(k, cf, a, st);
   }
-  if (cp.MT == 2) {       // hidden > 64: the wide kernel, always one tile per workgroup (the backward pass may take two)
+  if constexpr (!TRI) if (cp.MT == 2) {       // hidden > 64: the wide kernel, always one tile per workgroup (the backward pass may take two)
     CoopPlan cf = cp;
     if (cp.NT != 1) {
       int rc = coop_build_plan(pl, a.n, 1, false, &cf);
@@ -782,11 +784,15 @@ int co_fwd_k(const NsfPlan& pl, const CoopPlan& cp, const CoFwdArgs& a, hipStrea
     int rc = coop_build_plan(pl, a.n, 1, false, &cf);
     if (rc) return rc;
     coop_make_consts(pl, cf, &k);
-    return pl.KSH == 13 ? co_launch_fwd<K, 13, 1, true>(k, cf, a, st) : co_launch_fwd<K, 16, 1, true>(k, cf, a, st);
+    return pl.KSH == 13 ? co_launch_fwd<K, 13, 1, true, false, TRI>(k, cf, a, st)
+                        : co_launch_fwd<K, 16, 1, true, false, TRI>(k, cf, a, st);
   }
   coop_make_consts(pl, cp, &k);
-  if (pl.KSH == 13) return cp.NT == 2 ? co_launch_fwd<K, 13, 2, false>(k, cp, a, st) : co_launch_fwd<K, 13, 1, false>(k, cp, a, st);
-  return cp.NT == 2 ? co_launch_fwd<K, 16, 2, false>(k, cp, a, st) : co_launch_fwd<K, 16, 1, false>(k, cp, a, st);
+  if (pl.KSH == 13)
+    return cp.NT == 2 ? co_launch_fwd<K, 13, 2, false, false, TRI>(k, cp, a, st)
+                      : co_launch_fwd<K, 13, 1, false, false, TRI>(k, cp, a, st);
+  return cp.NT == 2 ? co_launch_fwd<K, 16, 2, false, false, TRI>(k, cp, a, st)
+                    : co_launch_fwd<K, 16, 1, false, false, TRI>(k, cp, a, st);
 }
 // sampling direction: wide nets at every batch size; narrow nets (MT = 1 instantiation of the same kernel) for the small
 // calls the cooperative family takes -- above, they keep the throughput kernel nsf_flow_kernel<..., INV = true>

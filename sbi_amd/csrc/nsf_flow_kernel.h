@@ -60,7 +60,10 @@ static bool flow_plan_is_static(const NsfPlan& pl, const NsfPlan& st) {
 // not running parks its flow state in registers (zs rows: 3 per lane, ld_acc) and swaps it back in with swap_tiles;
 // its context is re-read per transform.  Every row sees the same arithmetic in the same order as with TW = 1
 // (bit-identical results; stash layouts per 16-row tile and per row as before).
-template <int K, int KSH, bool INV, int SP = 0, bool BX = false, bool PREC = true, int TW = 1>
+// TRI (density direction, no stash): iid trials against a batch of conditions, nothing materialised -- x_rows is then
+// the number of trials, row r takes condition r / x_rows and input r % x_rows (sbi_amd_nsf_log_prob_trials, nsf_trials.hip);
+// every row sees the arithmetic of the paired call at the same row count
+template <int K, int KSH, bool INV, int SP = 0, bool BX = false, bool PREC = true, int TW = 1, bool TRI = false>
 __global__ void __launch_bounds__(INV ? 768 : 512)
 nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float* __restrict__ zstats,
                 const float* __restrict__ in, const float* __restrict__ x, long long n, long long x_rows,
@@ -75,6 +78,7 @@ nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float
   constexpr int PT = (3 * K - 1 + 15) / 16;
   static_assert(TW == 1 || (TW == 2 && SP == 8 && !INV && !BX && kStaticFlow8.C <= 16),
                 "two tiles per wave: static 8-wave density direction with the context in registers only");
+  static_assert(!TRI || (!INV && !BX && TW == 1), "iid trials: density direction, one tile per wave, no broadcast fold");
   const NsfPlan& pl = SP == 8 ? kStaticFlow8 : (SP == 12 ? kStaticFlow12 : pl_);   // LAYOUT only; floats / debug: pl_
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
@@ -165,9 +169,10 @@ nsf_flow_kernel(const NsfPlan pl_, const float* __restrict__ packed, const float
   for (int i = id.lane; i < pl.sc_total; i += 64) sc[i] = 0.f;   // no uninitialised LDS behind short rows
   // ---- load + z-score (PointwiseAffineTransform fwd / Standardize) ----
   for (int s = 0; s < TW; ++s) {
-    const long long xr = (x_rows == n) ? row : (x_rows == 1 ? 0 : row % x_rows);
+    const long long xr = TRI ? row / x_rows : ((x_rows == n) ? row : (x_rows == 1 ? 0 : row % x_rows));
+    const long long ir = TRI ? row - xr * x_rows : row;     // TRI: the trial this row evaluates
     for (int d = id.g; d < D; d += 4) {
-      float v = valid ? in[row * D + d] : 0.f;
+      float v = valid ? in[ir * D + d] : 0.f;
       if (!INV) {
         v = v * th_scale[d] + th_shift[d];
         ld_acc += logf(fabsf(th_scale[d]));
@@ -408,17 +413,17 @@ static inline bool nsf_flow_two_tiles(int64_t n, int nw) {
   return 2 * r2 <= r1;
 }
 
-template <int K, int KSH, bool INV, int SP = 0, bool BX = false, bool PREC = true, int TW = 1>
+template <int K, int KSH, bool INV, int SP = 0, bool BX = false, bool PREC = true, int TW = 1, bool TRI = false>
 static int launch_flow(const NsfPlan& pl, int nw, const float* packed, const float* zstats, const float* in,
                        const float* x, int64_t n, int64_t x_rows, float* out_main, float* out_aux,
                        float* z_stash, float* astash, float* pstash, hipStream_t stream) {
-  if constexpr (!BX && PREC) {
+  if constexpr (!BX && PREC && !TRI) {
     if (nsf_bx_applies(pl, nw, x_rows, z_stash, astash))
       return launch_flow<K, KSH, INV, SP, true>(pl, nw, packed, zstats, in, x, n, x_rows, out_main, out_aux, z_stash,
                                                 astash, pstash, stream);
   }
   const int64_t lds_bytes = nsf_lds_bytes(pl, nw) + (BX ? nsf_bx_extra_bytes(pl) : 0);
-  auto kern = nsf_flow_kernel<K, KSH, INV, SP, BX, PREC, TW>;
+  auto kern = nsf_flow_kernel<K, KSH, INV, SP, BX, PREC, TW, TRI>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (e != hipSuccess) return (int)e;
   const int64_t rows_per_wg = 16 * nw * TW;

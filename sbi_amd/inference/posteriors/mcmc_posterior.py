@@ -179,49 +179,27 @@ class MCMCPosterior:
         prior, logit map of a box, identity on an unbounded prior), theta = T^-1(u) and log|det| come from
         `sbi_amd_mcmc_to_constrained`, log q from the batched log_prob kernel, and the subtraction happens inside
         the tick kernel.  Returns None when anything does not match (the generic path is always correct)."""
-        import torch.distributions.transforms as tf
-        from torch.distributions import constraints
-
         from sbi_amd import _lib
+        from sbi_amd.inference.potentials.likelihood_based_potential import LikelihoodBasedPotential
         from sbi_amd.inference.potentials.posterior_based_potential import PosteriorBasedPotential
         from sbi_amd.neural_nets.estimators.nsf_flow import NSFFlow
 
         pot = self.potential_fn
-        if not isinstance(pot, PosteriorBasedPotential) or not isinstance(pot.posterior_estimator, NSFFlow):
-            return None
         if torch.device(self._device).type != "cuda":
+            return None
+        if isinstance(pot, LikelihoodBasedPotential):
+            return self._fused_likelihood_potential(pot)
+        if not isinstance(pot, PosteriorBasedPotential) or not isinstance(pot.posterior_estimator, NSFFlow):
             return None
         x_o = reshape_to_batch_event(pot.x_o, pot.posterior_estimator.condition_shape)
         if x_o.shape[0] != 1:
             return None
-        try:
-            support = pot.prior.support
-        except (NotImplementedError, AttributeError):
-            return None
-        base_c = support.base_constraint if hasattr(support, "base_constraint") else support
-        t = self._to_constrained                         # unconstrained -> constrained
-        if isinstance(t, tf.IndependentTransform):
-            t = t.base_transform
         D = pot.posterior_estimator.input_shape[0]
-        dev = torch.device(self._device)
-
-        def vec(v):
-            return torch.as_tensor(v, dtype=torch.float32, device=dev).expand(D).contiguous()
-
-        unbounded = isinstance(base_c, constraints._Real)
-        if isinstance(t, tf.ComposeTransform) and len(t.parts) == 0 and unbounded:
-            kind, p0, p1 = 0, None, None
-        elif isinstance(t, tf.AffineTransform) and unbounded:
-            kind, p0, p1 = 1, vec(t.loc), vec(t.scale)
-        elif (isinstance(t, tf.ComposeTransform) and len(t.parts) == 2 and isinstance(t.parts[0], tf.SigmoidTransform)
-              and isinstance(t.parts[1], tf.AffineTransform) and isinstance(base_c, constraints._Interval)):
-            low, high = vec(base_c.lower_bound), vec(base_c.upper_bound)
-            p0, p1 = vec(t.parts[1].loc), vec(t.parts[1].scale)
-            if not (torch.allclose(p0, low) and torch.allclose(p0 + p1, high)):
-                return None                              # the box of the transform is not the prior's support
-            kind = 2
-        else:
+        spec = self._constrained_map(pot.prior, D)
+        if spec is None:
             return None
+        kind, p0, p1 = spec
+        dev = torch.device(self._device)
         lib = _lib.load()
         net = pot.posterior_estimator.net
         # the kernels take the EMBEDDED condition (standardizing_net -> embedding_net in front of the flow,
@@ -251,15 +229,103 @@ class MCMCPosterior:
         potential_.fused_spec = (kind, p0, p1, log_q, net, x_row)
         return potential_
 
+    def _fused_likelihood_potential(self, pot) -> Optional[Callable]:
+        """NLE's potential in the same tick structure: theta = T^-1(u) and log|det| from `sbi_amd_mcmc_to_constrained`,
+        sum_i log q(x_i | theta) from the trials kernel (sbi_amd_nsf_log_prob_trials) plus log p(theta), the subtraction
+        inside the tick kernel.  The persistent sampler (sbi_amd_mcmc_slice_run) evaluates NPE's density with x_o as
+        the condition, so the spec is marked for the two-launch loop.  None when anything does not match."""
+        from sbi_amd import _lib
+        from sbi_amd.neural_nets.estimators.nsf_flow import NSFFlow, NSFNet
+
+        est = pot.likelihood_estimator
+        if not isinstance(est, NSFFlow) or type(est)._raw_log_prob is not NSFFlow._raw_log_prob:
+            return None
+        if not isinstance(est.net, NSFNet) or est._embedding_net is not None or not pot.x_is_iid:
+            return None
+        dev = torch.device(self._device)
+        x_trials = pot.x_o.reshape(-1, est.input_shape[0]).to(dev, torch.float32).contiguous()
+        lib = _lib.load()
+        if lib.sbi_amd_nsf_log_prob_trials_workspace_floats(est.net.hyper.c_config(), x_trials.shape[0], 1) < 0:
+            return None                                  # (hidden 65 - 128: no trials kernel)
+        D = int(est.condition_shape[0])
+        spec = self._constrained_map(pot.prior, D)
+        if spec is None:
+            return None
+        kind, p0, p1 = spec
+        prior = pot.prior
+
+        def log_q(theta: Tensor) -> Tensor:      # sum over the trials (one pass, no pairs) + log prior
+            ll = est.log_prob_iid_trials(x_trials, theta)
+            if ll is None:
+                raise RuntimeError("sbi_amd: the trials kernel refused a configuration it accepted before")
+            return ll + prior.log_prob(theta)
+
+        def potential_(u: Tensor):
+            u = u.to(torch.float32).contiguous()
+            C = u.shape[0]
+            theta = torch.empty_like(u)
+            lad = torch.empty(C, dtype=torch.float32, device=u.device)
+            with torch.cuda.device(u.device):
+                rc = lib.sbi_amd_mcmc_to_constrained(kind, C, D, _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(u),
+                                                     _lib.ptr(theta), _lib.ptr(lad), _lib.current_stream(u.device))
+            _lib.check(rc, "mcmc_to_constrained")
+            return log_q(theta), lad
+
+        potential_.fused_spec = (kind, p0, p1, log_q, None, None)
+        potential_.persistent_capable = False
+        return potential_
+
+    def _constrained_map(self, prior, D: int):
+        """(kind, p0, p1) of `sbi_amd_mcmc_to_constrained` for the parameter transform, or None: z-scoring of an
+        unbounded prior, logit map of a box, identity on an unbounded prior."""
+        import torch.distributions.transforms as tf
+        from torch.distributions import constraints
+
+        try:
+            support = prior.support
+        except (NotImplementedError, AttributeError):
+            return None
+        base_c = support.base_constraint if hasattr(support, "base_constraint") else support
+        t = self._to_constrained                         # unconstrained -> constrained
+        if isinstance(t, tf.IndependentTransform):
+            t = t.base_transform
+        dev = torch.device(self._device)
+
+        def vec(v):
+            return torch.as_tensor(v, dtype=torch.float32, device=dev).expand(D).contiguous()
+
+        unbounded = isinstance(base_c, constraints._Real)
+        if isinstance(t, tf.ComposeTransform) and len(t.parts) == 0 and unbounded:
+            kind, p0, p1 = 0, None, None
+        elif isinstance(t, tf.AffineTransform) and unbounded:
+            kind, p0, p1 = 1, vec(t.loc), vec(t.scale)
+        elif (isinstance(t, tf.ComposeTransform) and len(t.parts) == 2 and isinstance(t.parts[0], tf.SigmoidTransform)
+              and isinstance(t.parts[1], tf.AffineTransform) and isinstance(base_c, constraints._Interval)):
+            low, high = vec(base_c.lower_bound), vec(base_c.upper_bound)
+            p0, p1 = vec(t.parts[1].loc), vec(t.parts[1].scale)
+            if not (torch.allclose(p0, low) and torch.allclose(p0 + p1, high)):
+                return None                              # the box of the transform is not the prior's support
+            kind = 2
+        else:
+            return None
+        return kind, p0, p1
+
     def _get_initial_params(self, init_strategy: str, num_chains: int, **kwargs) -> Tensor:
         """mcmc_posterior.py:517-659, all chains in one batched call."""
+        from sbi_amd.inference.potentials.likelihood_based_potential import LikelihoodBasedPotential
+
+        potential_fn = self.potential_fn
+        if isinstance(potential_fn, LikelihoodBasedPotential):
+            # the init weights are detached: evaluate NLE's candidates (10 000 x num_trials pairs) with the trials kernel
+            def potential_fn(theta, _pot=self.potential_fn):
+                return _pot(theta, track_gradients=False)
         if init_strategy == "proposal":
             init = proposal_init(self.proposal, transform=self.theta_transform, num_chains=num_chains, **kwargs)
         elif init_strategy == "sir":
-            init = sir_init(self.proposal, self.potential_fn, transform=self.theta_transform, num_chains=num_chains,
+            init = sir_init(self.proposal, potential_fn, transform=self.theta_transform, num_chains=num_chains,
                             **kwargs)
         elif init_strategy == "resample":
-            init = resample_given_potential_fn(self.proposal, self.potential_fn, transform=self.theta_transform,
+            init = resample_given_potential_fn(self.proposal, potential_fn, transform=self.theta_transform,
                                                num_chains=num_chains, **kwargs)
         elif init_strategy == "latest_sample":
             stored = self._mcmc_init_params

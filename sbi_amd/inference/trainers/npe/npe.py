@@ -239,6 +239,10 @@ class PosteriorEstimatorTrainer:
         mk = torch.cat([t for t, r in zip(self._prior_masks, self._data_round_index) if r >= starting_round])
         return th, xx, mk
 
+    def _input_condition(self, theta: Tensor, x: Tensor):
+        """(flow input, condition) of the training pairs: a posterior estimator models theta given x (NLE swaps them)."""
+        return theta, x
+
     # ------------------------------------------------------------------ distributed helpers
     @staticmethod
     def _dist():
@@ -345,8 +349,7 @@ class PosteriorEstimatorTrainer:
             for p in list(net.parameters()) + list(net.buffers()):
                 p.data.copy_(self._bcast(p.data))
 
-        theta_d = theta.to(self._device)
-        x_d = x.to(self._device)
+        theta_d, x_d = self._input_condition(theta.to(self._device), x.to(self._device))
         masks_d = prior_masks.to(self._device)
         prior = self._prior
         train_idx = self.train_indices.to(self._device)

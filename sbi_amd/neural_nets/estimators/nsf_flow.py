@@ -366,6 +366,37 @@ def _log_prob_call(net: NSFNet, theta: Tensor, x: Tensor, want_noise: bool) -> T
     return logp, noise
 
 
+def log_prob_trials_call(net: NSFNet, x_trials: Tensor, theta: Tensor,
+                         want_rows: bool = False) -> Optional[Tuple[Tensor, Optional[Tensor]]]:
+    """NLE's iid-trial log-likelihood: x_trials (num_trials, D) flow inputs, theta (num_theta, C) embedded conditions ->
+    (sum over trials (num_theta,), per-row values (num_theta * num_trials,) theta-major | None), without materialising
+    the pairs (sbi_amd_nsf_log_prob_trials).  None when the kernels have no trials mode for this configuration (hidden
+    65 - 128): the caller evaluates the expanded pairs instead."""
+    dev = _lib.require_device(x_trials, theta, net.flat_params, net.zstats)
+    lib = _lib.load()
+    cfg = net.hyper.c_config()
+    num_trials, num_theta = int(x_trials.shape[0]), int(theta.shape[0])
+    ws = lib.sbi_amd_nsf_log_prob_trials_workspace_floats(cfg, num_trials, num_theta)
+    if ws == _lib.E_UNSUPPORTED:
+        return None
+    if ws < 0:
+        _lib.check(int(ws), "nsf_log_prob_trials_workspace_floats")
+    loglik = torch.empty(num_theta, dtype=torch.float32, device=dev)
+    rows = torch.empty(int(ws), dtype=torch.float32, device=dev)    # per-row values: returned, or the workspace
+    if ws == 0:
+        return loglik, (rows if want_rows else None)
+    packed = packed_weights(net, rows=int(ws))
+    with torch.cuda.device(dev):
+        rc = lib.sbi_amd_nsf_log_prob_trials(cfg, _lib.ptr(packed), _lib.ptr(net.zstats), _lib.ptr(x_trials), num_trials,
+                                             _lib.ptr(theta), num_theta, _lib.ptr(loglik),
+                                             _lib.ptr(rows) if want_rows else None, _lib.ptr(rows),
+                                             _lib.current_stream(dev))
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    _lib.check(rc, "nsf_log_prob_trials")
+    return loglik, (rows if want_rows else None)
+
+
 def _sample_call(net: NSFNet, noise: Tensor, x: Tensor, want_ld: bool) -> Tuple[Tensor, Optional[Tensor]]:
     dev = _lib.require_device(noise, x, net.flat_params, net.zstats)
     lib = _lib.load()
@@ -601,6 +632,20 @@ class NSFFlow(ConditionalDensityEstimator):
         dev = net.flat_params.device
         theta, ld = self._raw_sample(net, noise.to(dev), x.to(dev), want_ld)
         return theta.to(noise.device), (None if ld is None else ld.to(noise.device))
+
+    def log_prob_iid_trials(self, input: Tensor, condition: Tensor) -> Optional[Tensor]:
+        """sum_i log q(input_i | condition_c) for every condition row c (NLE's potential over iid trials): input
+        (num_trials, D), condition (num_theta, *condition_shape) -> (num_theta,), one pass over the pairs without building
+        them.  None when this estimator or configuration has no trials kernel (the caller then expands the pairs)."""
+        if type(self)._raw_log_prob is not NSFFlow._raw_log_prob or not isinstance(self.net, NSFNet):
+            return None                      # another family behind the NSF surface (maf_rqs): no trials kernel
+        with torch.no_grad():
+            x_trials = input.reshape(-1, self.input_shape[0]).contiguous().float()
+            theta = self._embed(condition).reshape(-1, self._cdim).contiguous().float()
+            net = self._kernel_net()
+            dev = net.flat_params.device
+            out = log_prob_trials_call(net, x_trials.to(dev), theta.to(dev))
+        return None if out is None else out[0].to(condition.device)
 
     def _autograd_log_prob(self, theta: Tensor, x: Tensor) -> Tensor:
         net = self._kernel_net()

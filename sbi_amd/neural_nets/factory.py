@@ -1,4 +1,4 @@
-"""``posterior_nn`` factory for the accelerated path.
+"""``posterior_nn`` / ``likelihood_nn`` factories for the accelerated path.
 
 Same call signature and behaviours as sbi/neural_nets/factory.py:323-430 for
 ``model="nsf"``: returns ``build_fn(batch_theta, batch_x)``; unknown kwargs warn
@@ -58,6 +58,42 @@ def posterior_nn(
             extra_kwargs=unknown, **known,
         )
         return cfg.build(batch_theta, batch_x)
+
+    return build_fn
+
+
+def likelihood_nn(
+    model: str,
+    z_score_theta: Optional[str] = "independent",
+    z_score_x: Optional[str] = "independent",
+    hidden_features: int = 50,
+    num_transforms: int = 5,
+    num_bins: int = 10,
+    embedding_net: nn.Module = nn.Identity(),
+    **kwargs: Any,
+) -> Callable[[Tensor, Tensor], nn.Module]:
+    """Return ``build_fn(batch_theta, batch_x)`` for a LIKELIHOOD estimator q(x | theta) (sbi/neural_nets/factory.py:
+    244-315): the NSF with x as the flow input and theta as the condition (z_score_x z-scores the input,
+    z_score_theta the condition, `embedding_net` embeds theta).  Only ``model="nsf"`` runs on the kernels; sbi's other
+    likelihood models (its default affine "maf", "mdn", "made", "maf_rqs", the zuko flows) are refused here."""
+    if model != "nsf":
+        raise NotImplementedError(
+            f"sbi_amd implements the 'nsf' likelihood estimator only (got model={model!r}); other model families are "
+            "outside the accelerated path. Use likelihood_nn('nsf')."
+        )
+    known = {k: v for k, v in kwargs.items() if k in _NSF_FIELDS}
+    unknown = {k: v for k, v in kwargs.items() if k not in _NSF_FIELDS}
+    if unknown:
+        warnings.warn(f"Unknown kwargs {sorted(unknown)} are forwarded to the builder.", UserWarning, stacklevel=2)
+
+    def build_fn(batch_theta: Tensor, batch_x: Tensor):
+        cfg = NSFConfig(
+            z_score_input=z_score_x, z_score_condition=z_score_theta,
+            embedding_net=None if isinstance(embedding_net, nn.Identity) else embedding_net,
+            hidden_features=hidden_features, num_transforms=num_transforms, num_bins=num_bins,
+            extra_kwargs=unknown, **known,
+        )
+        return cfg.build(batch_x, batch_theta)
 
     return build_fn
 

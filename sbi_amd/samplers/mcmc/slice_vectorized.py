@@ -71,7 +71,9 @@ class SliceSamplerVectorized:
             # Persistent form first: `poll_every` ticks of every chain per launch (a workgroup owns 16 chains and
             # alternates their log-density with their tick; sbi_amd_mcmc_slice_run).  Configurations the cooperative
             # kernels do not take fall back to two launches per tick.
-            persistent = bool(getattr(self, "persistent", True))
+            # (a spec marked persistent_capable = False -- NLE's likelihood over trials -- is not the density that
+            # kernel evaluates, x_o as the condition of theta)
+            persistent = bool(getattr(self, "persistent", True)) and getattr(self._log_prob_fn, "persistent_capable", True)
             if persistent:
                 from sbi_amd.neural_nets.estimators.nsf_flow import packed_weights
 
