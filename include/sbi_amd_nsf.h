@@ -337,8 +337,81 @@ int sbi_amd_rq_spline(int32_t num_bins, int32_t inverse, float tail_bound, float
  * -1 = the configuration has no cooperative image. */
 int sbi_amd_nsf_coop_selfcheck(const sbi_amd_nsf_config* cfg);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * NRE: the ResNet ratio classifier (csrc/nre.hip, csrc/nre_kernel.h)
+ *
+ * sbi's build_resnet_classifier (sbi/neural_nets/net_builders/classifier.py:172-235): standardized theta and x,
+ * concatenated [z_theta ; z_x], through nflows' ResidualNet(in = D + C, out = 1, hidden H, no context, NB blocks, relu,
+ * no dropout, no batch norm).  The logit is log r(theta, x) = RatioEstimator.unnormalized_log_ratio.
+ *   - `params`: flat buffer in nflows' order: initial_layer.weight (H, D + C), .bias (H); per block b:
+ *     linear_layers.0.weight (H, H), .bias (H), linear_layers.1.weight (H, H), .bias (H); final_layer.weight (1, H),
+ *     .bias (1).  sbi_amd_nre_param_offset(cfg, layer, bias): layer 0 initial, 1 + 2 b + i block b's linear i,
+ *     2 NB + 1 final; bias 0 / 1 = the weight / the bias.
+ *   - `packed`: sbi_amd_nre_packed_floats(cfg) floats, rebuilt by sbi_amd_nre_pack whenever params changed.
+ *   - `zstats`: 2 D + 2 C floats: theta mean (D), theta std (D), x mean (C), x std (C) (Standardize: (v - mean) / std).
+ *   - envelope: 1 <= D <= 64, 1 <= C <= 128, 1 <= H <= 64, 1 <= NB <= 4; anything else is SBI_AMD_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct sbi_amd_nre_config {
+  int32_t D;  /* theta features */
+  int32_t C;  /* (embedded) x features */
+  int32_t H;  /* hidden_features */
+  int32_t NB; /* num_blocks */
+} sbi_amd_nre_config;
+
+int64_t sbi_amd_nre_param_count(const sbi_amd_nre_config* cfg);
+int64_t sbi_amd_nre_param_offset(const sbi_amd_nre_config* cfg, int32_t layer, int32_t bias);
+int64_t sbi_amd_nre_packed_floats(const sbi_amd_nre_config* cfg);
+int sbi_amd_nre_pack(const sbi_amd_nre_config* cfg, const float* params, float* packed, void* stream);
+
+/* logit_out[r] = log r(theta_r, x[r % x_rows]) for n pairs (RatioEstimator.forward).  x_rows == 1 folds
+ * W_x z_x + b once per workgroup; the per-pair path computes that term with the same operations, so the two agree bit
+ * for bit. */
+int sbi_amd_nre_log_ratio(const sbi_amd_nre_config* cfg, const float* packed, const float* zstats, const float* theta,
+                          const float* x, int64_t n, int64_t x_rows, float* logit_out, void* stream);
+
+/* Ratio potential over iid trials: sum_out[c] = sum_i log r(theta_c, x_i), replacing _log_ratios_over_trials
+ * (sbi/inference/potentials/ratio_based_potential.py:122-160).  Row r = c * num_trials + i reads theta[c] and
+ * x_trials[i] in place; row_out (num_trials * num_theta, optional) receives the per-row values, bit-identical to
+ * sbi_amd_nre_log_ratio on the materialised pairs.  Each theta's trials are summed in fp64 in an order fixed by the trial
+ * index alone: repeat calls and permutations of theta are bit-exact.  workspace: ..._workspace_floats floats (unused
+ * when row_out is given). */
+int64_t sbi_amd_nre_log_ratio_trials_workspace_floats(const sbi_amd_nre_config* cfg, int64_t num_trials,
+                                                      int64_t num_theta);
+int sbi_amd_nre_log_ratio_trials(const sbi_amd_nre_config* cfg, const float* packed, const float* zstats,
+                                 const float* x_trials, int64_t num_trials, const float* theta, int64_t num_theta,
+                                 float* sum_out, float* row_out, float* workspace, void* stream);
+
+/* Training, as three launches per step (plus sbi_amd_adam_clip_step and sbi_amd_nre_pack):
+ *   sbi_amd_nre_train_forward: logits of n pairs (theta_r, x[r % x_rows]) and the activation stash in `workspace`
+ *     (sbi_amd_nre_train_workspace_floats(cfg, n) floats).  The atoms-major tensor of sbi_amd_atomic_atoms
+ *     (num_atoms, B, D) with x_rows = B is exactly the pairing of _classifier_logits (nre_base.py:396-415), reordered.
+ *   sbi_amd_nre_loss_weights: per-row losses loss_out (batch) and weights_out (optional, the logits' layout) =
+ *     scale * d(sum_b loss_out[b]) / d logit; logits atoms-major (atom a of row b at a * batch + b).  mode:
+ *       0 NRE_A (nre_a.py:165-189): num_atoms 2, nn.BCELoss on sigmoid, atom 0 labelled 1; loss_out[b] = the mean of
+ *         the row's two BCE terms (the log clamped at -100 as BCELoss does);
+ *       1 NRE_B (nre_b.py:157-182): loss_out[b] = logsumexp_a l - l_0;
+ *       2 NRE_C (nre_c.py:168-248): num_atoms = K + 1; logits hold the marginal set (K + 1 atoms, atom 0 unused) then
+ *         the joint set (K atoms, drawn independently); gamma > 0; log K pad, p_marginal / p_joint weights;
+ *       3 BNRE (bnre.py:167-202): mode 0 plus reg_strength * mean_b(sigmoid(l_0) + sigmoid(l_1) - 1)^2, added to every
+ *         row; the batch mean is reduced in a fixed order through `scratch` ((batch + 255) / 256 floats).
+ *     scale = 1 / batch gives the gradient of the reference's mean loss.
+ *   sbi_amd_nre_train_backward: from the per-pair weights (n) back through the network: grad_out (P, OVERWRITTEN) =
+ *     sum_r w_r d logit_r / d params, reduced over fixed row chunks in a fixed order (no atomics: repeat calls are
+ *     bit-identical); grad_theta_out (n, D, optional) = w_r d logit_r / d theta_r.  Same cfg, n and stream as the
+ *     forward whose stash it consumes. */
+int64_t sbi_amd_nre_train_workspace_floats(const sbi_amd_nre_config* cfg, int64_t n);
+int sbi_amd_nre_train_forward(const sbi_amd_nre_config* cfg, const float* packed, const float* zstats,
+                              const float* theta, const float* x, int64_t n, int64_t x_rows, float* logit_out,
+                              float* workspace, void* stream);
+int sbi_amd_nre_loss_weights(int32_t mode, const float* logits, int32_t batch, int32_t num_atoms, float gamma,
+                             float reg_strength, float scale, float* loss_out, float* weights_out, float* scratch,
+                             void* stream);
+int sbi_amd_nre_train_backward(const sbi_amd_nre_config* cfg, const float* packed, const float* zstats, int64_t n,
+                               const float* weights, float* grad_out, float* grad_theta_out, float* workspace,
+                               void* stream);
+
 /* Library/ABI version (major*100 + minor) and the gfx arch string it was built for. */
-#define SBI_AMD_NSF_ABI_VERSION 115
+#define SBI_AMD_NSF_ABI_VERSION 116
 int sbi_amd_nsf_abi_version(void);
 const char* sbi_amd_nsf_arch(void);
 

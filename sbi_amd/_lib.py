@@ -15,7 +15,7 @@ import torch
 from sbi_amd import _build
 
 _LIB: Optional[ctypes.CDLL] = None
-ABI_VERSION = 115    # must equal sbi_amd_nsf_abi_version() (csrc/nsf_plan.cpp) and SBI_AMD_NSF_ABI_VERSION (include/)
+ABI_VERSION = 116    # must equal sbi_amd_nsf_abi_version() (csrc/nsf_plan.cpp) and SBI_AMD_NSF_ABI_VERSION (include/)
 
 E_UNSUPPORTED, E_BADARG, E_LDS = -1, -2, -3
 _ERRORS = {
@@ -47,6 +47,12 @@ class MAFConfigC(Structure):
         ("tail_bound", c_float), ("min_bin_width", c_float), ("min_bin_height", c_float),
         ("min_derivative", c_float), ("scale_by_sqrt_hidden", c_int32), ("variant", c_int32),
     ]
+
+
+class NREConfigC(Structure):
+    """Mirror of ``struct sbi_amd_nre_config`` (include/sbi_amd_nsf.h, NRE section)."""
+
+    _fields_ = [("D", c_int32), ("C", c_int32), ("H", c_int32), ("NB", c_int32)]
 
 
 class FMPEConfigC(Structure):
@@ -204,6 +210,27 @@ _SIGNATURES = {
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
     "sbi_amd_nsf_plan_waves": (c_int, [POINTER(NSFConfigC), c_int64, c_int32]),
+    "sbi_amd_nre_param_count": (c_int64, [POINTER(NREConfigC)]),
+    "sbi_amd_nre_param_offset": (c_int64, [POINTER(NREConfigC), c_int32, c_int32]),
+    "sbi_amd_nre_packed_floats": (c_int64, [POINTER(NREConfigC)]),
+    "sbi_amd_nre_pack": (c_int, [POINTER(NREConfigC), c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_nre_log_ratio": (
+        c_int, [POINTER(NREConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "sbi_amd_nre_log_ratio_trials_workspace_floats": (c_int64, [POINTER(NREConfigC), c_int64, c_int64]),
+    "sbi_amd_nre_log_ratio_trials": (
+        c_int,
+        [POINTER(NREConfigC), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+         c_void_p],
+    ),
+    "sbi_amd_nre_train_workspace_floats": (c_int64, [POINTER(NREConfigC), c_int64]),
+    "sbi_amd_nre_train_forward": (
+        c_int,
+        [POINTER(NREConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+    "sbi_amd_nre_loss_weights": (
+        c_int, [c_int32, c_void_p, c_int32, c_int32, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_nre_train_backward": (
+        c_int, [POINTER(NREConfigC), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sbi_amd_nsf_abi_version": (c_int, []),
     "sbi_amd_nsf_arch": (c_char_p, []),
 }

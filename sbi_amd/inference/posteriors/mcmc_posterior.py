@@ -189,6 +189,10 @@ class MCMCPosterior:
             return None
         if isinstance(pot, LikelihoodBasedPotential):
             return self._fused_likelihood_potential(pot)
+        from sbi_amd.inference.potentials.ratio_based_potential import RatioBasedPotential
+
+        if isinstance(pot, RatioBasedPotential):
+            return self._fused_ratio_potential(pot)
         if not isinstance(pot, PosteriorBasedPotential) or not isinstance(pot.posterior_estimator, NSFFlow):
             return None
         x_o = reshape_to_batch_event(pot.x_o, pot.posterior_estimator.condition_shape)
@@ -275,6 +279,45 @@ class MCMCPosterior:
         potential_.persistent_capable = False
         return potential_
 
+    def _fused_ratio_potential(self, pot) -> Optional[Callable]:
+        """NRE's potential in the same two-launch tick structure as NLE's: theta = T^-1(u) and log|det| from
+        `sbi_amd_mcmc_to_constrained`, sum_i log r(theta, x_i) from the trials kernel (sbi_amd_nre_log_ratio_trials)
+        plus log p(theta), the subtraction inside the tick kernel.  None when anything does not match."""
+        from sbi_amd import _lib
+        from sbi_amd.neural_nets.estimators.ratio_estimator import RatioEstimator
+
+        est = pot.ratio_estimator
+        if not isinstance(est, RatioEstimator) or not pot.x_is_iid:
+            return None
+        dev = torch.device(self._device)
+        h = est.net.hyper
+        x_trials = pot.x_o.reshape(-1, h.C).to(dev, torch.float32).contiguous()
+        D = h.D
+        spec = self._constrained_map(pot.prior, D)
+        if spec is None:
+            return None
+        kind, p0, p1 = spec
+        lib = _lib.load()
+        prior = pot.prior
+
+        def log_q(theta: Tensor) -> Tensor:      # sum over the trials (one pass, no pairs) + log prior
+            return est.log_ratio_iid_trials(x_trials, theta) + prior.log_prob(theta)
+
+        def potential_(u: Tensor):
+            u = u.to(torch.float32).contiguous()
+            C = u.shape[0]
+            theta = torch.empty_like(u)
+            lad = torch.empty(C, dtype=torch.float32, device=u.device)
+            with torch.cuda.device(u.device):
+                rc = lib.sbi_amd_mcmc_to_constrained(kind, C, D, _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(u),
+                                                     _lib.ptr(theta), _lib.ptr(lad), _lib.current_stream(u.device))
+            _lib.check(rc, "mcmc_to_constrained")
+            return log_q(theta), lad
+
+        potential_.fused_spec = (kind, p0, p1, log_q, None, None)
+        potential_.persistent_capable = False
+        return potential_
+
     def _constrained_map(self, prior, D: int):
         """(kind, p0, p1) of `sbi_amd_mcmc_to_constrained` for the parameter transform, or None: z-scoring of an
         unbounded prior, logit map of a box, identity on an unbounded prior."""
@@ -315,7 +358,9 @@ class MCMCPosterior:
         from sbi_amd.inference.potentials.likelihood_based_potential import LikelihoodBasedPotential
 
         potential_fn = self.potential_fn
-        if isinstance(potential_fn, LikelihoodBasedPotential):
+        from sbi_amd.inference.potentials.ratio_based_potential import RatioBasedPotential
+
+        if isinstance(potential_fn, (LikelihoodBasedPotential, RatioBasedPotential)):
             # the init weights are detached: evaluate NLE's candidates (10 000 x num_trials pairs) with the trials kernel
             def potential_fn(theta, _pot=self.potential_fn):
                 return _pot(theta, track_gradients=False)

@@ -291,6 +291,21 @@ class PosteriorEstimatorTrainer:
 
         return perm
 
+    # ------------------------------------------------------------------ hooks of the epoch loop (NRE overrides them)
+    def _fused_training(self, net: nn.Module, calibration_kernel, emb_trainable: bool, atomic: bool) -> bool:
+        """Whether the steps run as one fused device pass with the flat-buffer optimizer (else autograd + torch Adam)."""
+        return (isinstance(net, NSFFlow) and torch.device(self._device).type == "cuda" and calibration_kernel is None
+                and not emb_trainable and (not atomic or getattr(net.net, "supports_atomic", False)))
+
+    def _make_stepper(self, net: nn.Module, cfg: TrainConfig, dist_mod):
+        from sbi_amd.inference.trainers.fused import FusedTrainStep
+
+        return FusedTrainStep(net, lr=cfg.learning_rate, clip_max_norm=cfg.clip_max_norm, distributed=dist_mod is not None)
+
+    def _first_round_losses(self, net: nn.Module, theta: Tensor, x: Tensor) -> Tensor:
+        """Per-row losses of a batch without the atomic correction (validation, and training off the fused path)."""
+        return net.loss(theta, x)
+
     # ------------------------------------------------------------------ training
     def train(self, num_atoms: int = 10, training_batch_size: int = 200, learning_rate: float = 5e-4,
               validation_fraction: float = 0.1, stop_after_epochs: int = 20, max_num_epochs: int = 2**31 - 1,
@@ -361,14 +376,10 @@ class PosteriorEstimatorTrainer:
         # (a frozen / parameter-free embedding still has to be APPLIED: FusedTrainStep embeds under no_grad)
         emb_trainable = any(p.requires_grad for p in net.embedding_net.parameters()) \
             if getattr(net, "embedding_net", None) is not None else False
-        fused = (isinstance(net, NSFFlow) and torch.device(self._device).type == "cuda" and calibration_kernel is None
-                 and not emb_trainable and (not atomic or getattr(net.net, "supports_atomic", False)))
+        fused = self._fused_training(net, calibration_kernel, emb_trainable, atomic)
         if not cfg.resume_training or (fused and self._stepper is None) or (not fused and self.optimizer is None):
             if fused:
-                from sbi_amd.inference.trainers.fused import FusedTrainStep
-
-                self._stepper = FusedTrainStep(net, lr=cfg.learning_rate, clip_max_norm=cfg.clip_max_norm,
-                                               distributed=d is not None)
+                self._stepper = self._make_stepper(net, cfg, d)
             else:
                 self.optimizer = torch.optim.Adam(params, lr=cfg.learning_rate)
             self.epoch, self._val_loss = 0, float("Inf")
@@ -391,7 +402,7 @@ class PosteriorEstimatorTrainer:
         def net_losses(th: Tensor, xx: Tensor, mk: Tensor) -> Tensor:
             """npe_base.py:542-575: MLE in the first round, proposal-corrected atomic loss afterwards."""
             if not atomic:
-                return net.loss(th, xx)
+                return self._first_round_losses(net, th, xx)
             return -log_prob_proposal_posterior_atomic(net, prior, th, xx, mk, self._num_atoms,
                                                        self._use_combined_loss)
 

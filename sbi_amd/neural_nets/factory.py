@@ -14,7 +14,8 @@ from typing import Any, Callable, Optional
 
 from torch import Tensor, nn
 
-from sbi_amd.neural_nets.net_builders.estimator_configs import MAFRQSConfig, NSFConfig, ZukoNSFConfig
+from sbi_amd.neural_nets.net_builders.estimator_configs import (MAFRQSConfig, NSFConfig, ResNetClassifierConfig,
+                                                                ZukoNSFConfig)
 
 _NSF_FIELDS = {"hidden_features", "num_transforms", "num_bins", "num_blocks", "dropout_probability",
                "use_batch_norm", "tail_bound", "hidden_layers_spline_context", "dtype"}
@@ -104,3 +105,37 @@ def posterior_flow_nn(*args, **kwargs):
     from sbi_amd.inference.trainers.vfpe.fmpe import posterior_flow_nn as _impl
 
     return _impl(*args, **kwargs)
+
+
+_RESNET_FIELDS = {"num_blocks", "dropout_probability", "use_batch_norm"}
+
+
+def classifier_nn(
+    model: str,
+    z_score_theta: Optional[str] = "independent",
+    z_score_x: Optional[str] = "independent",
+    hidden_features: int = 50,
+    embedding_net_theta: nn.Module = nn.Identity(),
+    embedding_net_x: nn.Module = nn.Identity(),
+    **kwargs: Any,
+) -> Callable[[Tensor, Tensor], nn.Module]:
+    """Return ``build_fn(batch_theta, batch_x)`` for NRE's ratio classifier (sbi/neural_nets/factory.py:174-235).  Only
+    ``model="resnet"`` (sbi's default, ``ResNetClassifierConfig``) runs on the kernels; "linear" and "mlp", dropout,
+    batch norm and non-identity embedding nets are refused with ``NotImplementedError``."""
+    if model != "resnet":
+        raise NotImplementedError(
+            f"sbi_amd implements the 'resnet' ratio classifier only (got model={model!r}); the 'linear' and 'mlp' "
+            "classifiers are outside the accelerated path. Use classifier_nn('resnet')."
+        )
+    known = {k: v for k, v in kwargs.items() if k in _RESNET_FIELDS}
+    unknown = {k: v for k, v in kwargs.items() if k not in _RESNET_FIELDS}
+    if unknown:
+        warnings.warn(f"Unknown kwargs {sorted(unknown)} are ignored by the 'resnet' classifier.", UserWarning,
+                      stacklevel=2)
+    cfg = ResNetClassifierConfig(
+        z_score_input=z_score_theta, z_score_condition=z_score_x,
+        embedding_net_theta=None if isinstance(embedding_net_theta, nn.Identity) else embedding_net_theta,
+        embedding_net_x=None if isinstance(embedding_net_x, nn.Identity) else embedding_net_x,
+        hidden_features=hidden_features, **known,
+    )
+    return cfg.build

@@ -120,3 +120,58 @@ class ZukoNSFConfig:
                               num_transforms=self.num_transforms, num_bins=self.num_bins,
                               embedding_net=nn.Identity() if self.embedding_net is None else self.embedding_net,
                               **self.extra_kwargs)
+
+
+@dataclass(frozen=True)
+class ResNetClassifierConfig:
+    """sbi's ``ResNetClassifierConfig`` (estimator_configs.py:1397-1411): the residual-network ratio classifier of NRE
+    (``build_resnet_classifier``).  ``build(batch_theta, batch_x)`` returns a ``RatioEstimator`` on the NRE kernels;
+    dropout, batch norm and embedding nets other than the identity are refused (``NotImplementedError``)."""
+
+    z_score_input: Optional[str] = "independent"
+    z_score_condition: Optional[str] = "independent"
+    embedding_net_theta: Optional[nn.Module] = None
+    embedding_net_x: Optional[nn.Module] = None
+    hidden_features: int = 50
+    num_blocks: int = 2
+    dropout_probability: float = 0.0
+    use_batch_norm: bool = False
+
+    def __post_init__(self):
+        for name in ("z_score_input", "z_score_condition"):
+            v = getattr(self, name)
+            if v is not None and v not in ("none", "independent", "structured"):
+                raise ValueError(f"{name}={v!r}: ratio classifiers take 'none', 'independent' or 'structured'.")
+        if self.dropout_probability > 0 or self.use_batch_norm:
+            raise NotImplementedError("The 'resnet' classifier runs on the kernels without dropout and batch norm "
+                                      "(dropout_probability=0.0, use_batch_norm=False).")
+        for name in ("embedding_net_theta", "embedding_net_x"):
+            net = getattr(self, name)
+            if net is not None and not isinstance(net, nn.Identity):
+                raise NotImplementedError(f"{name}: the 'resnet' classifier on the kernels takes no embedding net "
+                                          "(nn.Identity() only).")
+
+    def build(self, batch_theta: Tensor, batch_x: Tensor):
+        from sbi_amd.neural_nets.estimators.ratio_estimator import RatioEstimator, RatioHyper, RatioNet
+        from sbi_amd.utils.sbiutils import standardizing_stats, z_score_parser
+
+        th, xx = batch_theta.reshape(batch_theta.shape[0], -1), batch_x.reshape(batch_x.shape[0], -1)
+        D, C = th.shape[1], xx.shape[1]
+        zstats = torch.cat([torch.zeros(D), torch.ones(D), torch.zeros(C), torch.ones(C)])
+        zt, st = z_score_parser(self.z_score_input)
+        if zt:
+            m, s = standardizing_stats(th.float().cpu(), st)
+            zstats[:D], zstats[D : 2 * D] = m.expand(D), s.expand(D)
+        zx, sx = z_score_parser(self.z_score_condition)
+        if zx:
+            m, s = standardizing_stats(xx.float().cpu(), sx)
+            zstats[2 * D : 2 * D + C], zstats[2 * D + C :] = m.expand(C), s.expand(C)
+        hyper = RatioHyper(D, C, self.hidden_features, self.num_blocks)
+        from sbi_amd import _lib
+
+        if not (1 <= D <= 64 and 1 <= C <= 128 and 1 <= hyper.H <= 64 and 1 <= hyper.NB <= 4):
+            raise RuntimeError(f"sbi_amd: ratio classifier with theta-dim {D}, x-dim {C}, hidden_features {hyper.H}, "
+                               f"num_blocks {hyper.NB}: {_lib._ERRORS[_lib.E_UNSUPPORTED]} (NRE: theta-dim <= 64, "
+                               "x-dim <= 128, hidden_features <= 64, num_blocks <= 4)")
+        net = RatioNet(hyper, zstats)
+        return RatioEstimator(net, batch_theta.shape[1:], batch_x.shape[1:], z_score_theta=zt, z_score_x=zx)
