@@ -64,6 +64,15 @@ class FMPEConfigC(Structure):
     ]
 
 
+class NPSEConfigC(Structure):
+    """Mirror of ``struct sbi_amd_npse_config`` (include/sbi_amd_npse.h)."""
+
+    _fields_ = [
+        ("net", FMPEConfigC), ("sde", c_int32), ("weight", c_int32), ("beta_min", c_float), ("beta_max", c_float),
+        ("sigma_min", c_float), ("sigma_max", c_float), ("cv_threshold", c_float), ("t_min", c_float), ("t_max", c_float),
+    ]
+
+
 _SIGNATURES = {
     "sbi_amd_nsf_param_count": (c_int64, [POINTER(NSFConfigC)]),
     "sbi_amd_nsf_layer_offset": (c_int64, [POINTER(NSFConfigC), c_int32]),
@@ -236,8 +245,38 @@ _SIGNATURES = {
 }
 
 
+# include/sbi_amd_npse.h (the NPSE path; `exported_symbols_npse()` is what its header is checked against)
+_SIGNATURES_NPSE = {
+    "sbi_amd_npse_score": (
+        c_int,
+        [POINTER(NPSEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32,
+         c_void_p, c_void_p],
+    ),
+    "sbi_amd_npse_loss": (
+        c_int,
+        [POINTER(NPSEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+         c_void_p, c_void_p],
+    ),
+    "sbi_amd_npse_train_workspace_floats": (c_int64, [POINTER(NPSEConfigC), c_int64]),
+    "sbi_amd_npse_loss_fwd_bwd": (
+        c_int,
+        [POINTER(NPSEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+         c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "sbi_amd_npse_sample_sde": (
+        c_int,
+        [POINTER(NPSEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_float, c_void_p,
+         c_uint64, c_int64, c_int64, c_void_p, c_void_p],
+    ),
+}
+
+
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+def exported_symbols_npse():
+    return list(_SIGNATURES_NPSE)
 
 
 def load(build_if_missing: bool = True) -> ctypes.CDLL:
@@ -284,7 +323,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
         raise RuntimeError(f"{path} is stale (built from different sources); rebuild it with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(str(path))
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

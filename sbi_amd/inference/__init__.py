@@ -6,3 +6,4 @@ from sbi_amd.inference.trainers.npe.npe import NPE, NPE_C, SNPE  # noqa: F401
 from sbi_amd.inference.trainers.nre.nre import (AALR, BNRE, CNRE, NRE, NRE_A, NRE_B, NRE_C, SNRE, SNRE_A,  # noqa: F401
                                                 SNRE_B, SNRE_C, SRE)
 from sbi_amd.inference.trainers.vfpe.fmpe import FMPE, posterior_flow_nn  # noqa: F401
+from sbi_amd.inference.trainers.vfpe.npse import NPSE, posterior_score_nn  # noqa: F401

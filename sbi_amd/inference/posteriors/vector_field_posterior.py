@@ -1,10 +1,20 @@
-"""Posterior that samples a flow-matching estimator by solving its probability-flow ODE on the device.
+"""Posterior that samples a vector-field estimator on the device: the probability-flow ODE of a flow-matching or score
+estimator, or the reverse SDE of a score estimator (NPSE) with the fused Euler-Maruyama kernel.
 
 Mirror of sbi's ``VectorFieldPosterior`` for ``sample_with="ode"``
 (sbi/inference/posteriors/vector_field_posterior.py:155-330, 436-466): draw theta_1 ~ N(mean_base, std_base),
 integrate d theta / dt = v(theta, t; x_o) from t_max to t_min, reject draws outside the prior support.
 ``log_prob`` integrates the same ODE in the other direction together with the exact divergence of the vector field
 (zuko's exact-trace transform in sbi; here one HIP launch returns velocity and Jacobian trace).
+
+``sample_with="sde"`` (:331-434 -> samplers/score/diffuser.py:124-172, predictors.py:112-120) is for score estimators:
+draw theta ~ N(mean_base, std_base) at ``ts[0]`` and take ``len(ts) - 1`` Euler-Maruyama steps of the reverse SDE, all in
+one launch per batch (``sbi_amd_npse_sample_sde``).  The draws come from Philox keyed by a seed taken from torch's
+generator once per call and indexed by the candidate's running number, so for a given ``torch.manual_seed`` the returned
+samples do NOT depend on how ``max_sampling_batch_size`` splits the work.  Refused with ``NotImplementedError``:
+correctors, predictors other than "euler_maruyama", iid observations (several rows of ``x`` outside
+``sample_batched``: sbi's fnpe / gauss / auto_gauss / jac_gauss score composition) and ``log_prob`` of a score-based
+posterior (it needs the divergence of ``ode_fn``).
 """
 
 from __future__ import annotations
@@ -20,7 +30,10 @@ from sbi_amd.utils.sbiutils import within_support
 
 class VectorFieldPosterior:
     def __init__(self, vector_field_estimator, prior, device: Optional[str] = None, atol: float = 1e-6,
-                 rtol: float = 1e-5, max_sampling_batch_size: int = 100_000):
+                 rtol: float = 1e-5, max_sampling_batch_size: int = 100_000, sample_with: Optional[str] = None):
+        if sample_with not in (None, "ode", "sde"):
+            raise ValueError(f"sample_with must be 'ode' or 'sde', but is {sample_with}.")
+        self.sample_with = sample_with or "ode"
         self.vector_field_estimator = vector_field_estimator
         self.prior = prior
         self._device = device or str(next(vector_field_estimator.parameters()).device)
@@ -41,6 +54,10 @@ class VectorFieldPosterior:
         cshape = self.vector_field_estimator.condition_shape
         if x.dim() == len(cshape):
             x = x.unsqueeze(0)
+        if self._is_score() and x.dim() == len(cshape) + 1 and x.shape[0] > 1 and x.shape[1:] == cshape:
+            raise NotImplementedError("sbi_amd NPSE: iid observations (several rows of x: sbi's fnpe / gauss / auto_gauss"
+                                      " / jac_gauss score composition) are not implemented; one observation per call, "
+                                      "or sample_batched for independent observations")
         if x.shape[0] != 1 or x.shape[1:] != cshape:
             raise ValueError(f"expected one observation of shape {tuple(cshape)}, got {tuple(x.shape)}; use "
                              "sample_batched for several observations")
@@ -54,6 +71,44 @@ class VectorFieldPosterior:
                              "`x` explicitly.")
         return self._x
 
+    def _is_score(self) -> bool:
+        from sbi_amd.neural_nets.estimators.score_estimator import ConditionalScoreEstimator
+
+        return isinstance(self.vector_field_estimator, ConditionalScoreEstimator)
+
+    def _sde_setup(self, steps, ts, predictor, corrector, predictor_params, corrector_params, iid_method=None):
+        """Arguments of `_sample_via_diffusion` (vector_field_posterior.py:331-397) -> (ts on the device, eta, seed)."""
+        if not self._is_score():
+            raise NotImplementedError("sbi_amd FMPE posterior samples with the probability-flow ODE only")
+        if corrector is not None or corrector_params:
+            raise NotImplementedError("sbi_amd NPSE: correctors are not implemented (predictor-only Euler-Maruyama)")
+        if predictor != "euler_maruyama":
+            raise NotImplementedError(f"sbi_amd NPSE implements the 'euler_maruyama' predictor only, got {predictor!r}")
+        if iid_method is not None:
+            raise NotImplementedError("sbi_amd NPSE: iid score composition (iid_method) is not implemented")
+        params = dict(predictor_params or {})
+        eta = float(params.pop("eta", 1.0))
+        if params:
+            raise TypeError(f"unsupported predictor_params: {sorted(params)}")
+        if not eta > 0:
+            raise AssertionError("eta must be positive.")
+        est = self.vector_field_estimator
+        ts = est.solve_schedule(steps) if ts is None else torch.as_tensor(ts, dtype=torch.float32)
+        ts = ts.to(device=self._device, dtype=torch.float32).reshape(-1).contiguous()
+        seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
+        return ts, eta, seed
+
+    @torch.no_grad()
+    def sample_via_sde(self, num_samples: int, x: Tensor, ts: Tensor, eta: float = 1.0, seed: int = 0,
+                       row_offset: int = 0) -> Tensor:
+        from sbi_amd.neural_nets.estimators.score_estimator import sample_sde_fused, sample_sde_loop
+
+        est = self.vector_field_estimator
+        cond = (x if x.shape[0] == num_samples else x[:1]).contiguous()
+        if ts.numel() - 1 > 65535:        # beyond the fused kernel's step counter: one score launch per step
+            return sample_sde_loop(est, num_samples, cond, ts, eta)
+        return sample_sde_fused(est, num_samples, cond, ts, eta, None, seed, row_offset)
+
     @torch.no_grad()
     def sample_via_ode(self, num_samples: int, x: Tensor) -> Tensor:
         est = self.vector_field_estimator
@@ -66,16 +121,24 @@ class VectorFieldPosterior:
     @torch.no_grad()
     def sample(self, sample_shape=torch.Size(), x: Optional[Tensor] = None, max_sampling_batch_size: Optional[int] = None,
                sample_with: Optional[str] = None, show_progress_bars: bool = False,
-               reject_outside_prior: bool = True, **unsupported) -> Tensor:
-        if sample_with not in (None, "ode"):
-            raise NotImplementedError("sbi_amd FMPE posterior samples with the probability-flow ODE only")
+               reject_outside_prior: bool = True, predictor: str = "euler_maruyama", corrector: Optional[str] = None,
+               predictor_params: Optional[dict] = None, corrector_params: Optional[dict] = None, steps: int = 500,
+               ts: Optional[Tensor] = None, iid_method: Optional[str] = None, **unsupported) -> Tensor:
+        sample_with = sample_with or self.sample_with
+        if sample_with not in ("ode", "sde"):
+            raise ValueError(f"Expected sample_with to be 'ode' or 'sde', but got {sample_with}.")
+        if sample_with == "sde":
+            grid, eta, seed = self._sde_setup(steps, ts, predictor, corrector, predictor_params, corrector_params,
+                                              iid_method)
         x = self._x_else_default_x(x)
         num = int(torch.Size(sample_shape).numel())
         cap = max_sampling_batch_size or self.max_sampling_batch_size
-        out, have, tries = [], 0, 0
+        out, have, tries, drawn = [], 0, 0, 0
         while have < num:
             n = min(cap, max(num - have, 16))
-            draws = self.sample_via_ode(n, x)
+            draws = self.sample_via_ode(n, x) if sample_with == "ode" else \
+                self.sample_via_sde(n, x, grid, eta, seed, row_offset=drawn)
+            drawn += n
             if reject_outside_prior and self.prior is not None:
                 draws = draws[within_support(self.prior, draws)]
             out.append(draws)
@@ -86,13 +149,20 @@ class VectorFieldPosterior:
         return torch.cat(out)[:num].reshape(*torch.Size(sample_shape), -1)
 
     @torch.no_grad()
-    def sample_batched(self, sample_shape, x: Tensor, **kwargs) -> Tensor:
-        """(sample_shape, batch, D): every observation integrates its own draws in one batched ODE solve."""
+    def sample_batched(self, sample_shape, x: Tensor, predictor: str = "euler_maruyama", corrector: Optional[str] = None,
+                       predictor_params: Optional[dict] = None, corrector_params: Optional[dict] = None,
+                       steps: int = 500, ts: Optional[Tensor] = None, **kwargs) -> Tensor:
+        """(sample_shape, batch, D): every observation integrates its own draws in one batched ODE solve (or one
+        launch of the SDE sampler, every row conditioned on its own observation)."""
         x = torch.as_tensor(x, dtype=torch.float32).to(self._device)
         num = int(torch.Size(sample_shape).numel())
         B = x.shape[0]
         xs = x.repeat_interleave(num, dim=0).contiguous()
-        draws = self.sample_via_ode(num * B, xs)
+        if self.sample_with == "sde":
+            grid, eta, seed = self._sde_setup(steps, ts, predictor, corrector, predictor_params, corrector_params)
+            draws = self.sample_via_sde(num * B, xs, grid, eta, seed)
+        else:
+            draws = self.sample_via_ode(num * B, xs)
         return draws.reshape(B, num, -1).permute(1, 0, 2).reshape(*torch.Size(sample_shape), B, -1)
 
     @torch.no_grad()
@@ -113,6 +183,9 @@ class VectorFieldPosterior:
 
         ``ode_kwargs``: ``atol`` / ``rtol`` (defaults: the posterior's, sbi's 1e-6 / 1e-5); ``exact=False`` (zuko's
         Hutchinson estimate) is not offered."""
+        if self._is_score():
+            raise NotImplementedError("sbi_amd NPSE: log_prob of a score-based posterior is not implemented (it needs the "
+                                      "divergence of ode_fn); sample with 'sde' or 'ode'")
         if track_gradients:
             raise NotImplementedError("sbi_amd: log_prob of the flow-matching posterior does not track gradients")
         kw = dict(ode_kwargs or {})

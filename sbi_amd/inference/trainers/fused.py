@@ -403,3 +403,42 @@ class FusedFMPEStep(FusedTrainStep):
 
     def atomic_loss_and_grad(self, *a, **k):
         raise NotImplementedError("multi-round FMPE with arbitrary proposals is not implemented (as in sbi)")
+
+
+class FusedNPSEStep(FusedTrainStep):
+    """The device-resident step for the score estimators (NPSE): draw t from the estimator's ``train_schedule`` and
+    eps ~ N(0, I) on the device, fused denoising-score-matching loss (control variate below std 0.3, sbi's default)
+    forward + backward (csrc/npse.hip), [one all-reduce of the flat gradient], fused clip + Adam.  Replaces the loop
+    body of VectorFieldTrainer's training epoch (sbi/inference/trainers/vfpe/base_vf_inference.py:588-625)."""
+
+    control_variate_threshold = 0.3
+
+    def _workspace(self, n: int) -> Tensor:
+        from sbi_amd.neural_nets.estimators.score_estimator import train_workspace
+
+        self.workspace = train_workspace(self.est, n, self.net.flat_params.device, self.control_variate_threshold,
+                                         self.workspace)
+        return self.workspace
+
+    @torch.no_grad()
+    def loss_and_grad(self, theta: Tensor, x: Tensor, global_batch: Optional[int] = None,
+                      times: Optional[Tensor] = None, eps: Optional[Tensor] = None,
+                      row_weight: Optional[Tensor] = None) -> Tensor:
+        from sbi_amd.neural_nets.estimators.score_estimator import loss_fwd_bwd as dsm_loss_fwd_bwd
+
+        n = theta.shape[0]
+        gb = global_batch if global_batch is not None else n * self.world
+        if times is None:
+            times = self.est.train_schedule(n).to(device=theta.device, dtype=torch.float32).contiguous()
+        if eps is None:
+            eps = torch.randn_like(theta)
+        if row_weight is not None:
+            row_weight = (row_weight / gb).contiguous()
+        losses = dsm_loss_fwd_bwd(self.est, theta, x, times, eps, row_weight, 1.0 / gb, self.grad,
+                                  self.control_variate_threshold, workspace=self._workspace(n))
+        if self.distributed:
+            all_reduce_sum(self.dist, self.grad, self.group)
+        return losses
+
+    def atomic_loss_and_grad(self, *a, **k):
+        raise NotImplementedError("multi-round NPSE with arbitrary proposals is not implemented (as in sbi)")

@@ -109,14 +109,13 @@ class FMPE(PosteriorEstimatorTrainer):
         # sbi_amd's own estimator takes the fused HIP step (it refuses CPU tensors: no fallback); any other
         # vector-field estimator a user supplies (sbi lets `vf_estimator` be a custom builder) is trained
         # through autograd with the same loop, split, all-reduce and clipping
-        fused = isinstance(net, FlowMatchingEstimator)
+        step_cls = self._fused_step_cls(net)
+        fused = step_cls is not None
         params = [p for p in net.parameters() if p.requires_grad]
         if not cfg.resume_training or (fused and self._stepper is None) or (not fused and self.optimizer is None):
             if fused:
-                from sbi_amd.inference.trainers.fused import FusedFMPEStep
-
-                self._stepper = FusedFMPEStep(net, lr=cfg.learning_rate, clip_max_norm=cfg.clip_max_norm,
-                                              distributed=d is not None)
+                self._stepper = step_cls(net, lr=cfg.learning_rate, clip_max_norm=cfg.clip_max_norm,
+                                         distributed=d is not None)
             else:
                 self.optimizer = torch.optim.Adam(params, lr=cfg.learning_rate)
             self.epoch, self._val_loss = 0, float("Inf")
@@ -221,6 +220,15 @@ class FMPE(PosteriorEstimatorTrainer):
         if rank == 0:
             self._summarize(0)      # FMPE is single-round (fmpe.py:128-145)
         return deepcopy(net)
+
+    @staticmethod
+    def _fused_step_cls(net):
+        """The device-resident step for sbi_amd's own estimator, None for anything else (autograd path)."""
+        if isinstance(net, FlowMatchingEstimator):
+            from sbi_amd.inference.trainers.fused import FusedFMPEStep
+
+            return FusedFMPEStep
+        return None
 
     def _converged(self, epoch: int, stop_after_epochs: int) -> bool:
         """base_vf_inference.py:352-407: an epoch only counts as fruitless when the validation loss is more than

@@ -107,6 +107,21 @@ def posterior_flow_nn(*args, **kwargs):
     return _impl(*args, **kwargs)
 
 
+def posterior_score_nn(*args, **kwargs):
+    """``sbi.neural_nets.posterior_score_nn`` for the NPSE path (default MLP; ``sde_type`` "ve" | "vp" | "subvp"); see
+    ``sbi_amd.inference.trainers.vfpe.npse.posterior_score_nn`` (imported lazily: it needs the trainer package)."""
+    from sbi_amd.inference.trainers.vfpe.npse import posterior_score_nn as _impl
+
+    return _impl(*args, **kwargs)
+
+
+def build_score_matching_estimator(*args, **kwargs):
+    """``build_vector_field_estimator(..., estimator_type="score")`` for the configuration family the kernels run."""
+    from sbi_amd.neural_nets.estimators.score_estimator import build_score_matching_estimator as _impl
+
+    return _impl(*args, **kwargs)
+
+
 _RESNET_FIELDS = {"num_blocks", "dropout_probability", "use_batch_norm"}
 
 
