@@ -410,8 +410,26 @@ int sbi_amd_nre_train_backward(const sbi_amd_nre_config* cfg, const float* packe
                                const float* weights, float* grad_out, float* grad_theta_out, float* workspace,
                                void* stream);
 
+/* Persistent slice sampler for BATCHED sampling on the ratio classifier (csrc/nre_mcmc.hip): chain c of
+ * num_x * chains_per_x chains belongs to observation c / chains_per_x (x_obs: (num_x, C), one trial each) and is owned
+ * by ONE lane for the `nticks` ticks of a launch.  Each tick evaluates log r(theta_c, x_b) by the fma sequence of
+ * sbi_amd_nre_log_ratio (bit-identical), adds the prior term and runs the tick of sbi_amd_mcmc_slice_tick on the chain's
+ * own state (the same state arrays; uniforms always in-kernel: Philox, seed, tick0 + tick).  Only a box prior under the
+ * logit map is taken (kind == 2 of sbi_amd_mcmc_to_constrained; any other kind: SBI_AMD_E_UNSUPPORTED): its log-density
+ * is prior_log_prob on [prior_low, prior_high) per coordinate and -inf elsewhere.  theta_next (chains, D) holds the
+ * constrained image of next_param on entry (and on exit), logabsdet_next (chains) its log|det|; logp_scratch: chains
+ * floats.  wg_size: lanes per workgroup, 64 / 128 / 256, 0 = the default.  Poll *done_count between launches. */
+int sbi_amd_nre_mcmc_slice_run(const sbi_amd_nre_config* cfg, const float* packed, const float* zstats,
+                               const float* x_obs, int32_t num_x, int32_t chains_per_x, int32_t num_samples,
+                               int32_t tuning, float max_width, float* x, float* next_param, float* width,
+                               int32_t* order, int32_t* istate, float* fstate, float* samples, int32_t* done_count,
+                               uint64_t seed, uint64_t tick0, int32_t nticks, int32_t kind, const float* p0,
+                               const float* p1, const float* prior_low, const float* prior_high, float prior_log_prob,
+                               float* theta_next, float* logabsdet_next, float* logp_scratch, int32_t wg_size,
+                               void* stream);
+
 /* Library/ABI version (major*100 + minor) and the gfx arch string it was built for. */
-#define SBI_AMD_NSF_ABI_VERSION 116
+#define SBI_AMD_NSF_ABI_VERSION 117
 int sbi_amd_nsf_abi_version(void);
 const char* sbi_amd_nsf_arch(void);
 

@@ -227,3 +227,59 @@ nre_backward_kernel(NreDims d, const float* __restrict__ pk_, const float* __res
     }
   }
 }
+
+// The logit of ONE pair in two halves, for a lane that keeps its x: nre_x_part is W_x z_x + b (the first half of
+// nre_forward_kernel<HP, false, false>'s chain, in the same order), nre_logit_from_x_part continues from a copy of it with
+// the theta columns, the blocks and the final layer -- the same fma sequence, identical bits.
+template <int HP>
+__device__ __forceinline__ void nre_x_part(const NreDims& d, const nre_cfloat* pk, const nre_cfloat* zs,
+                                           const float* __restrict__ xr, float (&hx)[HP]) {
+  const nre_cfloat* WxT = pk + HP;
+#pragma unroll
+  for (int i = 0; i < HP; ++i) hx[i] = pk[i];
+  for (int k = 0; k < d.C; ++k) {
+    const float z = (xr[k] - zs[2 * d.D + k]) / zs[2 * d.D + d.C + k];
+#pragma unroll
+    for (int i = 0; i < HP; ++i) hx[i] = fmaf((WxT + k * HP)[i], z, hx[i]);
+  }
+}
+
+template <int HP>
+__device__ __forceinline__ float nre_logit_from_x_part(const NreDims& d, const nre_cfloat* pk, const nre_cfloat* zs,
+                                                       const float* tr, const float (&hx)[HP]) {
+  const nre_cfloat* WtT = pk + HP + (int64_t)d.C * HP;
+  float h[HP];
+#pragma unroll
+  for (int i = 0; i < HP; ++i) h[i] = hx[i];
+  for (int k = 0; k < d.D; ++k) {
+    const float z = (tr[k] - zs[k]) / zs[d.D + k];
+#pragma unroll
+    for (int i = 0; i < HP; ++i) h[i] = fmaf((WtT + k * HP)[i], z, h[i]);
+  }
+  for (int b = 0; b < d.NB; ++b) {
+    const nre_cfloat* L0 = pk + nre_pk_blk<HP>(d, b, 0);
+    const nre_cfloat* L1 = pk + nre_pk_blk<HP>(d, b, 1);
+    float u[HP];
+#pragma unroll
+    for (int i = 0; i < HP; ++i) u[i] = L0[HP * HP + i];
+#pragma unroll
+    for (int j = 0; j < HP; ++j) {
+      const float a = h[j] > 0.f ? h[j] : 0.f;
+#pragma unroll
+      for (int i = 0; i < HP; ++i) u[i] = fmaf((L0 + j * HP)[i], a, u[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < HP; ++i) h[i] += L1[HP * HP + i];
+#pragma unroll
+    for (int j = 0; j < HP; ++j) {
+      const float c = u[j] > 0.f ? u[j] : 0.f;
+#pragma unroll
+      for (int i = 0; i < HP; ++i) h[i] = fmaf((L1 + j * HP)[i], c, h[i]);
+    }
+  }
+  const nre_cfloat* F = pk + nre_pk_final<HP>(d);
+  float lg = 0.f;
+#pragma unroll
+  for (int i = 0; i < HP; ++i) lg = fmaf(F[i], h[i], lg);
+  return lg + F[HP];
+}

@@ -17,10 +17,19 @@ from torch import Tensor
 from sbi_amd import _lib
 
 
+# Whether batched sampling on the ratio classifier takes the one-lane-per-chain persistent kernel without being asked
+# (the sampler's `persistent=True / False` decides otherwise).  DESIGN.md section 7e holds the measurement behind the value.
+NRE_PERSISTENT_DEFAULT = True
+
+
 class SliceSamplerVectorized:
     def __init__(self, log_prob_fn: Callable[[Tensor], Tensor], init_params: Tensor, num_chains: int = 1,
                  thin: int = 1, tuning: int = 50, verbose: bool = False, init_width: float = 0.01,
-                 max_width: float = float("inf"), num_workers: int = 1, poll_every: int = 64):
+                 max_width: float = float("inf"), num_workers: int = 1, poll_every: int = 64,
+                 persistent: Optional[bool] = None, nre_wg_size: int = 0):
+        """`persistent`: True / False asks for / rules out the persistent kernels (several ticks per launch); None takes
+        each kernel's own default -- the NSF one wherever it applies, the NRE one per NRE_PERSISTENT_DEFAULT.
+        `nre_wg_size`: lanes per workgroup of the NRE persistent kernel (64 / 128 / 256; 0: its default, 64)."""
         self._log_prob_fn = log_prob_fn
         self.x = torch.as_tensor(init_params, dtype=torch.float32).contiguous()
         _lib.require_device(self.x)
@@ -33,9 +42,15 @@ class SliceSamplerVectorized:
         self.init_width = float(init_width)
         self.max_width = float(max_width)
         self.poll_every = int(poll_every)
+        self.persistent = persistent
+        self.nre_wg_size = int(nre_wg_size)
         self.n_dims = self.x.shape[1]
         self._samples: Optional[Tensor] = None
         self.num_ticks = 0
+        self.route: Optional[str] = None        # which tick route the last run took (diagnostics, tests)
+
+    def _wants_persistent(self, default: bool) -> bool:
+        return default if self.persistent is None else bool(self.persistent)
 
     @torch.no_grad()
     def run(self, num_samples: int) -> Tensor:
@@ -68,34 +83,69 @@ class SliceSamplerVectorized:
                 rc = lib.sbi_amd_mcmc_to_constrained(kind, C, D, _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nxt), _lib.ptr(theta),
                                                      _lib.ptr(lad), _lib.current_stream(dev))
             _lib.check(rc, "mcmc_to_constrained")
-            # Persistent form first: `poll_every` ticks of every chain per launch (a workgroup owns 16 chains and
-            # alternates their log-density with their tick; sbi_amd_mcmc_slice_run).  Configurations the cooperative
-            # kernels do not take fall back to two launches per tick.
-            # (a spec marked persistent_capable = False -- NLE's likelihood over trials -- is not the density that
-            # kernel evaluates, x_o as the condition of theta)
-            persistent = bool(getattr(self, "persistent", True)) and getattr(self._log_prob_fn, "persistent_capable", True)
-            if persistent:
+            # Persistent forms first: `poll_every` ticks of every chain per launch.  Each candidate is a closure that
+            # launches the ticks from `tick` on and returns the entry point's code; the first one that takes the
+            # configuration (no E_UNSUPPORTED from its first launch) runs the chains to the end.
+            #   * batched sampling on the ratio classifier, a lane owns a chain (sbi_amd_nre_mcmc_slice_run): refuses
+            #     every prior but a box under the logit map;
+            #   * one x_o for all chains on the NSF, a workgroup owns 16 chains (sbi_amd_mcmc_slice_run): refuses what
+            #     the cooperative kernels do not take.  A spec marked persistent_capable = False (NLE's likelihood over
+            #     trials, one observation per chain) is not the density that kernel evaluates and is not offered to it.
+            # Otherwise: two launches per tick.
+            candidates = []
+            nre = getattr(self._log_prob_fn, "nre_persistent", None)
+            if nre is not None and self._wants_persistent(NRE_PERSISTENT_DEFAULT):
+                if nre["num_x"] * nre["chains_per_x"] != C:
+                    raise ValueError(f"{nre['num_x']} observations x {nre['chains_per_x']} chains do not make {C} chains")
+                pk, zs = nre["net"].packed(dev)
+                nre_cfg = nre["net"].hyper.c_config()
+                nre_scratch = torch.empty(C, dtype=torch.float32, device=dev)
+
+                def launch_nre(tick0: int) -> int:
+                    return lib.sbi_amd_nre_mcmc_slice_run(
+                        nre_cfg, _lib.ptr(pk), _lib.ptr(zs), _lib.ptr(nre["x"]), nre["num_x"], nre["chains_per_x"],
+                        int(num_samples), self.tuning, max_width, _lib.ptr(x), _lib.ptr(nxt), _lib.ptr(width),
+                        _lib.ptr(order), _lib.ptr(istate), _lib.ptr(fstate), _lib.ptr(samples), _lib.ptr(done), seed,
+                        tick0, self.poll_every, kind, _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(nre["low"]),
+                        _lib.ptr(nre["high"]), nre["prior_log_prob"], _lib.ptr(theta), _lib.ptr(lad),
+                        _lib.ptr(nre_scratch), self.nre_wg_size, _lib.current_stream(dev))
+
+                candidates.append(("nre_persistent", launch_nre))
+            if getattr(self._log_prob_fn, "persistent_capable", True) and self._wants_persistent(True):
                 from sbi_amd.neural_nets.estimators.nsf_flow import packed_weights
 
                 packed = packed_weights(net, rows=None)
                 cfg = net.hyper.c_config()
                 scratch = torch.empty(C, dtype=torch.float32, device=dev)
-            while persistent:
+
+                def launch_nsf(tick0: int) -> int:
+                    return lib.sbi_amd_mcmc_slice_run(cfg, _lib.ptr(packed), _lib.ptr(net.zstats), _lib.ptr(x_row), C,
+                                                      int(num_samples), self.tuning, max_width, _lib.ptr(x), _lib.ptr(nxt),
+                                                      _lib.ptr(width), _lib.ptr(order), _lib.ptr(istate), _lib.ptr(fstate),
+                                                      _lib.ptr(samples), _lib.ptr(done), seed, tick0, self.poll_every, kind,
+                                                      _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(theta), _lib.ptr(lad),
+                                                      _lib.ptr(scratch), _lib.current_stream(dev))
+
+                candidates.append(("persistent", launch_nsf))
+            finished = False
+            for route, launch in candidates:
                 with torch.cuda.device(dev):
-                    rc = lib.sbi_amd_mcmc_slice_run(cfg, _lib.ptr(packed), _lib.ptr(net.zstats), _lib.ptr(x_row), C,
-                                                    int(num_samples), self.tuning, max_width, _lib.ptr(x), _lib.ptr(nxt),
-                                                    _lib.ptr(width), _lib.ptr(order), _lib.ptr(istate), _lib.ptr(fstate),
-                                                    _lib.ptr(samples), _lib.ptr(done), seed, tick, self.poll_every, kind,
-                                                    _lib.ptr(p0), _lib.ptr(p1), _lib.ptr(theta), _lib.ptr(lad),
-                                                    _lib.ptr(scratch), _lib.current_stream(dev))
-                if rc == _lib.E_UNSUPPORTED and tick == 0:
-                    persistent = False
-                    break
-                _lib.check(rc, "mcmc_slice_run")
-                tick += self.poll_every
-                if int(done.item()) == C:
-                    break
-            while not persistent:
+                    rc = launch(0)
+                if rc == _lib.E_UNSUPPORTED:
+                    continue
+                self.route = route
+                while True:
+                    _lib.check(rc, route)
+                    tick += self.poll_every
+                    if int(done.item()) == C:
+                        break
+                    with torch.cuda.device(dev):
+                        rc = launch(tick)
+                finished = True
+                break
+            if not finished:
+                self.route = "two_launch"
+            while not finished:
                 logp = log_q(theta)
                 with torch.cuda.device(dev):
                     rc = lib.sbi_amd_mcmc_slice_tick(C, D, int(num_samples), self.tuning, max_width, _lib.ptr(logp),
@@ -107,6 +157,8 @@ class SliceSamplerVectorized:
                 tick += 1
                 if tick % self.poll_every == 0 and int(done.item()) == C:
                     break
+        if fused is None:
+            self.route = "generic"
         while fused is None:
             out = self._log_prob_fn(nxt)
             # a (log_prob, offset) pair keeps the potential's "- log|det|" out of a separate launch

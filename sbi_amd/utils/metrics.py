@@ -49,3 +49,9 @@ def check_c2st(x: Tensor, y: Tensor, alg: str, tol: float = 0.1) -> None:
     assert (0.5 - tol) <= score <= (0.5 + tol), (
         f"{alg}'s c2st={score:.2f} is too far from the desired near-chance performance."
     )
+
+
+def l2(x: Tensor, y: Tensor, axis: int = -1) -> Tensor:
+    """Euclidean distance along `axis` (sbi/utils/metrics.py `l2`; the default distance of TARP)."""
+    return torch.sqrt(torch.sum((x - y) ** 2, dim=axis))
+
