@@ -13,6 +13,7 @@ from sbi_amd.samplers.mcmc import SliceSamplerVectorized
 from sbi_amd.simulators.linear_gaussian import linear_gaussian, true_posterior_linear_gaussian_mvn_prior
 from sbi_amd.utils.metrics import c2st
 from sbi_amd.utils.torchutils import BoxUniform
+from tests.mcmc_restatement import torch_tick as _torch_tick
 
 pytestmark = pytest.mark.gpu
 
@@ -93,57 +94,6 @@ def test_mcmc_posterior_matches_direct_posterior(prior_kind):
     assert torch.allclose(pot, direct.log_prob(s_direct[:10], norm_posterior=False), atol=1e-4)
     with pytest.raises(NotImplementedError):
         mcmc.sample((10,), method="nuts_pyro")
-
-
-def _torch_tick(st, logp, u, num_samples, tuning, max_width):
-    """Tensorised restatement of the per-chain transitions of slice_numpy.py:438-566 (test oracle for the
-    tick kernel; consumes the same uniforms)."""
-    x, nxt, width, order, state, i, t, cxi, wi, lx, ux, xi, logu, samples = (st[k] for k in (
-        "x", "nxt", "width", "order", "state", "i", "t", "cxi", "wi", "lx", "ux", "xi", "logu", "samples"))
-    C, D = x.shape
-    ar = torch.arange(C, device=x.device)
-    dim = order[ar, i]
-    live = state != 4
-    is_b, is_l, is_u, is_s = (live & (state == k) for k in range(4))
-    # BEGIN
-    cxi = torch.where(is_b, x[ar, dim], cxi)
-    wi = torch.where(is_b, width[ar, dim], wi)
-    logu = torch.where(is_b, logp + torch.log(1.0 - u[:, 0]), logu)
-    lx_b = cxi - wi * u[:, 1]
-    # LOWER
-    out_l = is_l & (logp >= logu) & (cxi - lx < max_width)
-    # UPPER
-    out_u = is_u & (logp >= logu) & (ux - cxi < max_width)
-    # SAMPLE
-    rej = is_s & (logp < logu)
-    acc = is_s & ~rej
-    new_lx = torch.where(is_b, lx_b, torch.where(out_l, lx - wi, torch.where(rej & (xi < cxi), xi, lx)))
-    new_ux = torch.where(is_b, lx_b + wi, torch.where(out_u, ux + wi, torch.where(rej & ~(xi < cxi), xi, ux)))
-    draw = (new_ux - new_lx) * u[:, 2] + new_lx
-    new_xi = torch.where((is_u & ~out_u) | rej, draw, xi)
-    val = torch.where(is_b | out_l, new_lx, torch.where((is_l & ~out_l) | out_u, new_ux, new_xi))
-    write = live & ~acc
-    nxt[ar[write], dim[write]] = val[write]
-    x[ar[acc], dim[acc]] = xi[acc]
-    tune = acc & (t < tuning)
-    w_old = width[ar[tune], dim[tune]]
-    width[ar[tune], dim[tune]] = w_old + ((ux[tune] - lx[tune]) - w_old) / (t[tune] + 1).float()
-    sweep_end = acc & (i == D - 1)
-    store = sweep_end & (t >= tuning)
-    samples[ar[store], (t[store] - tuning)] = x[store]
-    # fresh order by Fisher-Yates on the same uniforms
-    for c in ar[sweep_end].tolist():
-        o = list(range(D))
-        for d in range(D - 1, 0, -1):
-            k = min(int(float(u[c, 4 + d]) * (d + 1)), d)        # float32 product as in the kernel
-            o[d], o[k] = o[k], o[d]
-        order[c] = torch.tensor(o, dtype=order.dtype, device=order.device)
-    new_state = torch.where(is_b, 1, torch.where(is_l & ~out_l, 2, torch.where(is_u & ~out_u, 3,
-                            torch.where(acc, 0, state))))
-    t = torch.where(sweep_end, t + 1, t)
-    i = torch.where(acc, torch.where(sweep_end, torch.zeros_like(i), i + 1), i)
-    new_state = torch.where(sweep_end & (t >= num_samples + tuning), 4, new_state)
-    st.update(state=new_state, i=i, t=t, cxi=cxi, wi=wi, lx=new_lx, ux=new_ux, xi=new_xi, logu=logu)
 
 
 def test_tick_kernel_matches_tensorised_restatement_bit_for_bit():
