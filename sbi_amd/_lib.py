@@ -73,6 +73,16 @@ class NPSEConfigC(Structure):
     ]
 
 
+class LC2STConfigC(Structure):
+    """Mirror of ``struct sbi_amd_lc2st_config`` (include/sbi_amd_lc2st.h)."""
+
+    _fields_ = [
+        ("D", c_int32), ("Dx", c_int32), ("H", c_int32), ("B", c_int32), ("lr", c_float), ("weight_decay", c_float),
+        ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("patience", c_int32), ("threshold", c_float),
+        ("max_epochs", c_int32),
+    ]
+
+
 _SIGNATURES = {
     "sbi_amd_nsf_param_count": (c_int64, [POINTER(NSFConfigC)]),
     "sbi_amd_nsf_layer_offset": (c_int64, [POINTER(NSFConfigC), c_int32]),
@@ -277,8 +287,34 @@ _SIGNATURES_NPSE = {
 }
 
 
+# include/sbi_amd_lc2st.h (the L-C2ST classifier ensemble; `exported_symbols_lc2st()` is what its header is checked against)
+_SIGNATURES_LC2ST = {
+    "sbi_amd_lc2st_param_count": (c_int64, [POINTER(LC2STConfigC)]),
+    "sbi_amd_lc2st_train_epochs": (
+        c_int,
+        [POINTER(LC2STConfigC), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+         c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_int32, c_void_p],
+    ),
+    "sbi_amd_lc2st_batch_grad": (
+        c_int,
+        [POINTER(LC2STConfigC), c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+         c_uint64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
+    ),
+    "sbi_amd_lc2st_eval": (
+        c_int,
+        [POINTER(LC2STConfigC), c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+         c_void_p],
+    ),
+}
+
+
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+def exported_symbols_lc2st():
+    return list(_SIGNATURES_LC2ST)
 
 
 def exported_symbols_npse():
@@ -329,7 +365,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
         raise RuntimeError(f"{path} is stale (built from different sources); rebuild it with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(str(path))
-    for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE}.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

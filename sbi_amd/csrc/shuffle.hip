@@ -16,29 +16,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/sbi_amd_nsf.h"
-
-__host__ __device__ __forceinline__ uint32_t shf_mix(uint32_t v) {     // murmur3's 32-bit finaliser
-  v ^= v >> 16; v *= 0x85ebca6bu; v ^= v >> 13; v *= 0xc2b2ae35u; v ^= v >> 16;
-  return v;
-}
-// position i of the order -> element pi(i) of [0, n); hb = bits per Feistel half (2 hb >= ceil(log2 n))
-__host__ __device__ __forceinline__ uint32_t shf_prp(uint32_t i, uint32_t n, int hb, uint64_t key) {
-  const uint32_t mask = (1u << hb) - 1u;
-  const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-  uint32_t v = i;
-  do {
-    uint32_t l = v >> hb, r = v & mask;
-#pragma unroll
-    for (int round = 0; round < 6; ++round) {
-      const uint32_t f = shf_mix(r + 0x9e3779b9u * (uint32_t)(round + 1) + ((round & 1) ? k1 : k0)) & mask;
-      const uint32_t t = l ^ f;
-      l = r;
-      r = t;
-    }
-    v = (l << hb) | r;
-  } while (v >= n);
-  return v;
-}
+#include "shuffle_prp.h"
 
 __global__ void __launch_bounds__(256)
 shuffled_gather_kernel(const float* __restrict__ a, int da, const float* __restrict__ b, int db,

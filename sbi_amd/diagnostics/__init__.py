@@ -1,5 +1,7 @@
-"""Calibration diagnostics of a trained posterior: simulation-based calibration / expected coverage and TARP."""
+"""Calibration diagnostics of a trained posterior: simulation-based calibration / expected coverage, TARP and the local
+classifier two-sample test (L-C2ST)."""
 
+from sbi_amd.diagnostics.lc2st import LC2ST, LC2ST_NF, LC2STScores, LC2STState, permute_data  # noqa: F401
 from sbi_amd.diagnostics.sbc import (  # noqa: F401
     check_prior_vs_dap,
     check_sbc,
