@@ -49,6 +49,12 @@ class MAFConfigC(Structure):
     ]
 
 
+class MDNConfigC(Structure):
+    """Mirror of ``struct sbi_amd_mdn_config`` (include/sbi_amd_mdn.h)."""
+
+    _fields_ = [("D", c_int32), ("C", c_int32), ("H", c_int32), ("K", c_int32), ("epsilon", c_float)]
+
+
 class NREConfigC(Structure):
     """Mirror of ``struct sbi_amd_nre_config`` (include/sbi_amd_nsf.h, NRE section)."""
 
@@ -309,8 +315,34 @@ _SIGNATURES_LC2ST = {
 }
 
 
+# include/sbi_amd_mdn.h (the mixture-density-network posterior estimator)
+_SIGNATURES_MDN = {
+    "sbi_amd_mdn_param_count": (c_int64, [POINTER(MDNConfigC)]),
+    "sbi_amd_mdn_packed_floats": (c_int64, [POINTER(MDNConfigC)]),
+    "sbi_amd_mdn_param_offset": (c_int64, [POINTER(MDNConfigC), c_int32, c_int32]),
+    "sbi_amd_mdn_pack": (c_int, [POINTER(MDNConfigC), c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_mdn_components": (
+        c_int, [POINTER(MDNConfigC), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_mdn_log_prob": (
+        c_int, [POINTER(MDNConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "sbi_amd_mdn_sample": (
+        c_int,
+        [POINTER(MDNConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+         c_void_p]),
+    "sbi_amd_mdn_train_workspace_floats": (c_int64, [POINTER(MDNConfigC), c_int64]),
+    "sbi_amd_mdn_loss_fwd_bwd": (
+        c_int,
+        [POINTER(MDNConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
+
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+def exported_symbols_mdn():
+    return list(_SIGNATURES_MDN)
 
 
 def exported_symbols_lc2st():
@@ -365,7 +397,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
         raise RuntimeError(f"{path} is stale (built from different sources); rebuild it with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(str(path))
-    for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST}.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

@@ -443,6 +443,12 @@ class MCMCPosterior:
 
         # the slice sampler's tick kernel applies the transform itself (sbi_amd_mcmc_slice_tick): two launches per tick
         potential_.fused_spec = (kind, p0, p1, log_q, net, x_row)
+        # the persistent sampler (sbi_amd_mcmc_slice_run) evaluates the NSF itself from its packed image: any other
+        # family behind the NSFFlow surface (maf_rqs, zuko_nsf, mdn) keeps the two-launch tick on its own log_q
+        from sbi_amd.neural_nets.estimators.nsf_flow import NSFNet
+
+        if not isinstance(net, NSFNet):
+            potential_.persistent_capable = False
         return potential_
 
     def _fused_likelihood_potential(self, pot) -> Optional[Callable]:

@@ -405,6 +405,26 @@ class FusedFMPEStep(FusedTrainStep):
         raise NotImplementedError("multi-round FMPE with arbitrary proposals is not implemented (as in sbi)")
 
 
+class FusedMDNStep(FusedTrainStep):
+    """The device-resident step for the mixture density network: weight re-pack, fused mixture loss forward +
+    backward (csrc/mdn.hip; the gradient's fixed-order reduction is deterministic), fused clip + Adam.  `step`,
+    `loss_and_grad` and `apply` are the base class's (the net's `train_pass` is the MDN's; the clip norm comes from the
+    reduced gradient).  Single-round NPE on one device: the atomic proposal-posterior loss and data-parallel training
+    are refused by name."""
+
+    def __init__(self, estimator, lr: float = 5e-4, clip_max_norm: Optional[float] = 5.0, betas=(0.9, 0.999),
+                 eps: float = 1e-8):
+        from sbi_amd.neural_nets.estimators.mdn import MixtureDensityEstimator
+
+        if not isinstance(estimator, MixtureDensityEstimator):
+            raise TypeError(f"FusedMDNStep trains a MixtureDensityEstimator, got {type(estimator).__name__}")
+        super().__init__(estimator, lr=lr, clip_max_norm=clip_max_norm, betas=betas, eps=eps)
+
+    def atomic_loss_and_grad(self, *a, **k):
+        raise NotImplementedError("the mixture density network trains in single-round NPE only: the atomic "
+                                  "proposal-posterior loss of multi-round NPE-C is not implemented for it")
+
+
 class FusedNPSEStep(FusedTrainStep):
     """The device-resident step for the score estimators (NPSE): draw t from the estimator's ``train_schedule`` and
     eps ~ N(0, I) on the device, fused denoising-score-matching loss (control variate below std 0.3, sbi's default)

@@ -32,7 +32,7 @@ from torch.distributions import Distribution
 from sbi_amd.neural_nets.estimators.base import ConditionalDensityEstimator
 from sbi_amd.neural_nets.estimators.nsf_flow import NSFFlow
 from sbi_amd.neural_nets.factory import posterior_nn
-from sbi_amd.neural_nets.net_builders.estimator_configs import NSFConfig, ZukoNSFConfig
+from sbi_amd.neural_nets.net_builders.estimator_configs import MDNConfig, NSFConfig, ZukoNSFConfig
 from sbi_amd.utils.collectives import all_reduce_sum
 from sbi_amd.utils.sbiutils import handle_invalid_x, warn_on_invalid_x
 from sbi_amd.utils.torchutils import check_if_prior_on_device, process_device
@@ -74,7 +74,7 @@ def check_estimator_arg(estimator) -> None:
         )
     if isinstance(estimator, type):
         raise TypeError("Pass a config *instance* (e.g. NSFConfig()), not the config class.")
-    if not (isinstance(estimator, (str, NSFConfig, ZukoNSFConfig)) or callable(estimator)):
+    if not (isinstance(estimator, (str, NSFConfig, ZukoNSFConfig, MDNConfig)) or callable(estimator)):
         raise TypeError(f"Unsupported density_estimator argument of type {type(estimator).__name__}")
 
 
@@ -129,7 +129,7 @@ class PosteriorEstimatorTrainer:
                 "`from sbi_amd.neural_nets import NSFConfig`.", FutureWarning, stacklevel=3,
             )
             self._build_neural_net = posterior_nn(model=density_estimator)
-        elif isinstance(density_estimator, (NSFConfig, ZukoNSFConfig)):
+        elif isinstance(density_estimator, (NSFConfig, ZukoNSFConfig, MDNConfig)):
             self._build_neural_net = density_estimator.build
         else:
             self._build_neural_net = density_estimator
@@ -298,8 +298,14 @@ class PosteriorEstimatorTrainer:
                 and not emb_trainable and (not atomic or getattr(net.net, "supports_atomic", False)))
 
     def _make_stepper(self, net: nn.Module, cfg: TrainConfig, dist_mod):
-        from sbi_amd.inference.trainers.fused import FusedTrainStep
+        from sbi_amd.inference.trainers.fused import FusedMDNStep, FusedTrainStep
+        from sbi_amd.neural_nets.estimators.mdn import MixtureDensityEstimator
 
+        if isinstance(net, MixtureDensityEstimator):
+            if dist_mod is not None:
+                raise NotImplementedError("sbi_amd: multi-GPU training of the mixture density network is not "
+                                          "implemented; train it on one device")
+            return FusedMDNStep(net, lr=cfg.learning_rate, clip_max_norm=cfg.clip_max_norm)
         return FusedTrainStep(net, lr=cfg.learning_rate, clip_max_norm=cfg.clip_max_norm, distributed=dist_mod is not None)
 
     def _first_round_losses(self, net: nn.Module, theta: Tensor, x: Tensor) -> Tensor:
@@ -355,6 +361,13 @@ class PosteriorEstimatorTrainer:
                 raise TypeError("The density_estimator builder must return a ConditionalDensityEstimator.")
             self._stepper = None
         net = self._neural_net.to(self._device)
+        from sbi_amd.neural_nets.estimators.mdn import MixtureDensityEstimator
+
+        if atomic and isinstance(net, MixtureDensityEstimator):
+            raise NotImplementedError(
+                "sbi_amd: the mixture density network trains in single-round NPE only (simulations from the prior, or "
+                "force_first_round_loss=True); the proposal correction of multi-round NPE-C for mixtures (its "
+                "closed-form MoG form and NPE-A / mdn_snpe_a) is not implemented.")
         params = [p for p in net.parameters() if p.requires_grad]
         if not params:
             raise TypeError(f"{type(self).__name__} cannot train {type(net).__name__}: it has no trainable "
@@ -487,7 +500,7 @@ class PosteriorEstimatorTrainer:
 
         snap_ring = [None] * 4       # (at most three epoch records are alive at a time)
         if (fused and not atomic and n_train_batches <= 2 and isinstance(net, NSFFlow) and hasattr(net.net, "hyper")
-                and _os.environ.get("SBI_AMD_TAIL_EXTRA", "1") != "0"):
+                and not isinstance(net, MixtureDensityEstimator) and _os.environ.get("SBI_AMD_TAIL_EXTRA", "1") != "0"):
             # one or two steps per epoch, validation batches on the OTHER kernel family (e.g. batch 65 536 / 10 000
             # validation rows): let the step's table pack refresh the validation image too instead of a separate pack
             # launch every epoch

@@ -14,14 +14,15 @@ from typing import Any, Callable, Optional
 
 from torch import Tensor, nn
 
-from sbi_amd.neural_nets.net_builders.estimator_configs import (MAFRQSConfig, NSFConfig, ResNetClassifierConfig,
-                                                                ZukoNSFConfig)
+from sbi_amd.neural_nets.net_builders.estimator_configs import (MAFRQSConfig, MDNConfig, NSFConfig,
+                                                                ResNetClassifierConfig, ZukoNSFConfig)
 
 _NSF_FIELDS = {"hidden_features", "num_transforms", "num_bins", "num_blocks", "dropout_probability",
                "use_batch_norm", "tail_bound", "hidden_layers_spline_context", "dtype"}
 _MAF_RQS_FIELDS = (_NSF_FIELDS - {"hidden_layers_spline_context"}) | {"tails", "min_bin_width", "min_bin_height",
                                                                         "min_derivative"}
 _MODELS = {"nsf": (NSFConfig, _NSF_FIELDS), "maf_rqs": (MAFRQSConfig, _MAF_RQS_FIELDS)}
+_MDN_FIELDS = {"num_components"}
 
 
 def posterior_nn(
@@ -35,7 +36,7 @@ def posterior_nn(
     **kwargs: Any,
 ) -> Callable[[Tensor, Tensor], nn.Module]:
     """Return a function that builds the posterior density estimator from (theta, x) batches."""
-    model_fields = _MODELS.get(model, _MODELS["nsf"])[1]
+    model_fields = _MDN_FIELDS if model == "mdn" else _MODELS.get(model, _MODELS["nsf"])[1]
     known = {k: v for k, v in kwargs.items() if k in model_fields}
     unknown = {k: v for k, v in kwargs.items() if k not in model_fields}
     if unknown:
@@ -47,9 +48,23 @@ def posterior_nn(
                                  embedding_net=None if isinstance(embedding_net, nn.Identity) else embedding_net,
                                  hidden_features=hidden_features, num_transforms=num_transforms, num_bins=num_bins,
                                  extra_kwargs={**known, **unknown}).build(batch_theta, batch_x)
+        if model == "mdn":
+            if z_score_theta == "transform_to_unconstrained":
+                raise NotImplementedError("sbi_amd: posterior_nn('mdn', z_score_theta='transform_to_unconstrained') is "
+                                          "not implemented. Use one of 'none', 'independent', 'structured'.")
+            return MDNConfig(z_score_input=z_score_theta, z_score_condition=z_score_x,
+                             embedding_net=None if isinstance(embedding_net, nn.Identity) else embedding_net,
+                             hidden_features=hidden_features, extra_kwargs=unknown, **known).build(batch_theta, batch_x)
+        if model == "mdn_snpe_a":
+            raise NotImplementedError("sbi_amd: 'mdn_snpe_a' (the mixture density network of NPE-A, whose last layer is "
+                                      "trained with more components in the final round) is not implemented; NPE-A "
+                                      "itself is not either. Use posterior_nn('mdn') with single-round NPE.")
+        if model == "made":
+            raise NotImplementedError("sbi_amd: 'made' (MADE with a mixture-of-Gaussians output, MADE-MoG) is not "
+                                      "implemented. Use 'mdn', 'nsf', 'maf_rqs' or 'zuko_nsf'.")
         if model not in _MODELS:
             raise NotImplementedError(
-                f"sbi_amd implements the 'nsf', 'maf_rqs' and 'zuko_nsf' posterior estimators (got model={model!r}); other "
+                f"sbi_amd implements the 'nsf', 'maf_rqs', 'zuko_nsf' and 'mdn' posterior estimators (got model={model!r}); other "
                 "model families are outside the accelerated path."
             )
         cfg = _MODELS[model][0](

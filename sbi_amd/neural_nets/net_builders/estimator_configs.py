@@ -123,6 +123,38 @@ class ZukoNSFConfig:
 
 
 @dataclass(frozen=True)
+class MDNConfig:
+    """Mirror of sbi's ``MDNConfig``: the mixture-density-network posterior estimator (``build_mdn``)."""
+
+    z_score_input: Optional[str] = "independent"
+    z_score_condition: Optional[str] = "independent"
+    embedding_net: Optional[nn.Module] = None
+    hidden_features: int = 50
+    num_components: int = 10
+    extra_kwargs: Dict[str, Any] = field(default_factory=dict)
+
+    def __post_init__(self):
+        for name in ("z_score_input", "z_score_condition"):
+            v = getattr(self, name)
+            if v is None:
+                object.__setattr__(self, name, "none")
+            elif v not in _Z_SCORE_VALUES:
+                raise ValueError(f"{name} must be one of {_Z_SCORE_VALUES} or None, got {v!r}")
+        for name in ("hidden_features", "num_components"):
+            if int(getattr(self, name)) < 1:
+                raise ValueError(f"{name} must be a positive integer")
+
+    def build(self, batch_input: Tensor, batch_condition: Tensor):
+        from sbi_amd.neural_nets.net_builders.mdn import build_mdn
+
+        return build_mdn(batch_x=batch_input, batch_y=batch_condition, z_score_x=self.z_score_input,
+                         z_score_y=self.z_score_condition, hidden_features=self.hidden_features,
+                         num_components=self.num_components,
+                         embedding_net=nn.Identity() if self.embedding_net is None else self.embedding_net,
+                         **self.extra_kwargs)
+
+
+@dataclass(frozen=True)
 class ResNetClassifierConfig:
     """sbi's ``ResNetClassifierConfig`` (estimator_configs.py:1397-1411): the residual-network ratio classifier of NRE
     (``build_resnet_classifier``).  ``build(batch_theta, batch_x)`` returns a ``RatioEstimator`` on the NRE kernels;
