@@ -55,6 +55,16 @@ class MDNConfigC(Structure):
     _fields_ = [("D", c_int32), ("C", c_int32), ("H", c_int32), ("K", c_int32), ("epsilon", c_float)]
 
 
+class MNLEConfigC(Structure):
+    """Mirror of ``struct sbi_amd_mnle_config`` (include/sbi_amd_mnle.h)."""
+
+    _fields_ = [("V", c_int32), ("num_categories", c_int32 * 4), ("C", c_int32), ("discrete_hidden", c_int32),
+                ("discrete_blocks", c_int32), ("embedding", c_int32), ("hidden", c_int32), ("num_bins", c_int32),
+                ("num_transforms", c_int32), ("context_layers", c_int32), ("log_transform", c_int32),
+                ("tail_bound", c_float), ("min_bin_width", c_float), ("min_bin_height", c_float),
+                ("min_derivative", c_float)]
+
+
 class NREConfigC(Structure):
     """Mirror of ``struct sbi_amd_nre_config`` (include/sbi_amd_nsf.h, NRE section)."""
 
@@ -337,8 +347,38 @@ _SIGNATURES_MDN = {
 }
 
 
+# include/sbi_amd_mnle.h (mixed discrete / continuous likelihood estimator)
+_SIGNATURES_MNLE = {
+    "sbi_amd_mnle_param_count": (c_int64, [POINTER(MNLEConfigC)]),
+    "sbi_amd_mnle_packed_floats": (c_int64, [POINTER(MNLEConfigC)]),
+    "sbi_amd_mnle_param_offset": (c_int64, [POINTER(MNLEConfigC), c_int32, c_int32]),
+    "sbi_amd_mnle_pack": (c_int, [POINTER(MNLEConfigC), c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_mnle_log_prob": (
+        c_int,
+        [POINTER(MNLEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+         c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_mnle_log_prob_trials": (
+        c_int,
+        [POINTER(MNLEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+         c_void_p, c_void_p]),
+    "sbi_amd_mnle_sample": (
+        c_int,
+        [POINTER(MNLEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+         c_void_p]),
+    "sbi_amd_mnle_train_workspace_floats": (c_int64, [POINTER(MNLEConfigC), c_int64]),
+    "sbi_amd_mnle_loss_fwd_bwd": (
+        c_int,
+        [POINTER(MNLEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
+
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+def exported_symbols_mnle():
+    return list(_SIGNATURES_MNLE)
 
 
 def exported_symbols_mdn():
@@ -397,7 +437,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
         raise RuntimeError(f"{path} is stale (built from different sources); rebuild it with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(str(path))
-    for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN}.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
+                                      **_SIGNATURES_MNLE}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

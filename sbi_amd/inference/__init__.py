@@ -1,6 +1,7 @@
 from sbi_amd.inference.posteriors.direct_posterior import DirectPosterior  # noqa: F401
 from sbi_amd.inference.posteriors.mcmc_posterior import MCMCPosterior  # noqa: F401
 from sbi_amd.inference.posteriors.rejection_posterior import RejectionPosterior  # noqa: F401
+from sbi_amd.inference.trainers.nle.mnle import MNLE  # noqa: F401
 from sbi_amd.inference.trainers.nle.nle import NLE, NLE_A, SNLE  # noqa: F401
 from sbi_amd.inference.trainers.npe.npe import NPE, NPE_C, SNPE  # noqa: F401
 from sbi_amd.inference.trainers.nre.nre import (AALR, BNRE, CNRE, NRE, NRE_A, NRE_B, NRE_C, SNRE, SNRE_A,  # noqa: F401

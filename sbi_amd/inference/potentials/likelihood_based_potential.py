@@ -121,3 +121,27 @@ def likelihood_estimator_based_potential(likelihood_estimator: ConditionalDensit
     potential_fn = LikelihoodBasedPotential(likelihood_estimator, prior, x_o, device=device)
     theta_transform = mcmc_transform(prior, device=device, enable_transform=enable_transform)
     return potential_fn, theta_transform
+
+
+class MixedLikelihoodBasedPotential(LikelihoodBasedPotential):
+    """Deprecated thin alias (as in the reference): the mixed estimator goes through ``LikelihoodBasedPotential``."""
+
+    def __init__(self, *args, **kwargs):
+        import warnings
+
+        warnings.warn("MixedLikelihoodBasedPotential is deprecated; use LikelihoodBasedPotential.", DeprecationWarning,
+                      stacklevel=2)
+        super().__init__(*args, **kwargs)
+
+    def condition_on_theta(self, *args, **kwargs):
+        raise NotImplementedError("sbi_amd: condition_on_theta is not implemented for the mixed likelihood "
+                                  "potential; sample the full posterior and slice the draws")
+
+
+def mixed_likelihood_estimator_based_potential(likelihood_estimator, prior, x_o, enable_transform: bool = True):
+    """Deprecated thin alias of ``likelihood_estimator_based_potential``."""
+    import warnings
+
+    warnings.warn("mixed_likelihood_estimator_based_potential is deprecated; use "
+                  "likelihood_estimator_based_potential.", DeprecationWarning, stacklevel=2)
+    return likelihood_estimator_based_potential(likelihood_estimator, prior, x_o, enable_transform=enable_transform)

@@ -425,6 +425,34 @@ class FusedMDNStep(FusedTrainStep):
                                   "proposal-posterior loss of multi-round NPE-C is not implemented for it")
 
 
+class FusedMNLEStep(FusedTrainStep):
+    """The device-resident step for the mixed likelihood estimator (MNLE): weight re-pack, fused joint loss forward +
+    backward (csrc/mnle.hip: categorical MADE + 1-D spline flow; the gradient's fixed-order reduction is
+    deterministic), fused clip + Adam on the flat buffer.  `step(x, theta)`: the estimator's input is the data row
+    [continuous, categorical values], its condition theta.  Single device."""
+
+    def __init__(self, estimator, lr: float = 5e-4, clip_max_norm: Optional[float] = 5.0, betas=(0.9, 0.999),
+                 eps: float = 1e-8):
+        from sbi_amd.neural_nets.estimators.mixed_density_estimator import MixedDensityEstimator
+
+        if not isinstance(estimator, MixedDensityEstimator):
+            raise TypeError(f"FusedMNLEStep trains a MixedDensityEstimator, got {type(estimator).__name__}")
+        super().__init__(estimator, lr=lr, clip_max_norm=clip_max_norm, betas=betas, eps=eps)
+
+    def _embedded(self, x: Tensor) -> Tensor:
+        emb = self.est.embedding_net
+        if emb is None:
+            return x.contiguous().float()
+        if any(p.requires_grad for p in emb.parameters()):
+            raise RuntimeError("FusedMNLEStep cannot train a theta embedding net (its optimizer owns the flat "
+                               "parameter buffer only); use the autograd path of MNLE.train().")
+        with torch.no_grad():
+            return emb(x).reshape(x.shape[0], -1).contiguous().float()
+
+    def atomic_loss_and_grad(self, *a, **k):
+        raise NotImplementedError("MNLE trains with the plain likelihood loss; there is no atomic loss")
+
+
 class FusedNPSEStep(FusedTrainStep):
     """The device-resident step for the score estimators (NPSE): draw t from the estimator's ``train_schedule`` and
     eps ~ N(0, I) on the device, fused denoising-score-matching loss (control variate below std 0.3, sbi's default)

@@ -154,6 +154,67 @@ class MDNConfig:
                          **self.extra_kwargs)
 
 
+def _default_mixed_continuous() -> NSFConfig:
+    return NSFConfig(tail_bound=10.0)
+
+
+@dataclass(frozen=True)
+class MixedConfig:
+    """Mirror of sbi's ``MixedConfig`` (MNLE): the continuous part is configured by a nested ``NSFConfig`` (default
+    ``NSFConfig(tail_bound=10.0)``), whose z-scoring applies to the continuous column; ``z_score_condition`` here
+    applies to theta.  ``build(batch_input, batch_condition)`` returns a ``MixedDensityEstimator`` on the MNLE
+    kernels; continuous configs other than the NSF, dropout, a custom combined embedding net are refused
+    (``NotImplementedError``)."""
+
+    continuous: Any = field(default_factory=_default_mixed_continuous)
+    z_score_condition: Optional[str] = "independent"
+    num_categories_per_variable: Optional[Tensor] = None
+    embedding_net: Optional[nn.Module] = None
+    combined_embedding_net: Optional[nn.Module] = None
+    log_transform_x: bool = False
+    discrete_hidden_features: Optional[int] = None
+    discrete_hidden_layers: int = 2
+    combined_embedding_features: Optional[int] = None
+    dropout_probability: float = 0.0
+    extra_kwargs: Dict[str, Any] = field(default_factory=dict)
+
+    def __post_init__(self):
+        if self.z_score_condition is None:
+            object.__setattr__(self, "z_score_condition", "none")
+        elif self.z_score_condition not in ("none", "independent", "structured"):
+            raise ValueError(f"z_score_condition must be 'none', 'independent' or 'structured', got "
+                             f"{self.z_score_condition!r}")
+        if type(self.continuous) is not NSFConfig:
+            raise NotImplementedError(
+                f"sbi_amd MNLE: {type(self.continuous).__name__} cannot estimate the continuous component here; the "
+                "continuous part is the NSF only, use continuous=NSFConfig(...)")
+        if self.continuous.z_score_condition != "independent" or self.continuous.embedding_net is not None:
+            raise ValueError("The continuous config's `z_score_condition` and `embedding_net` are replaced when its "
+                             "mixed condition is built. Configure them with `MixedConfig.z_score_condition`, "
+                             "`embedding_net`, and `combined_embedding_net` instead.")
+        if self.extra_kwargs:
+            raise ValueError("MixedConfig has no downstream pass-through for `extra_kwargs`. Put continuous-model "
+                             "options in `continuous.extra_kwargs`.")
+        if self.dropout_probability > 0 or self.continuous.dropout_probability > 0:
+            raise NotImplementedError("sbi_amd MNLE: dropout_probability > 0 is not implemented; use 0.0")
+        if self.combined_embedding_net is not None:
+            raise NotImplementedError("sbi_amd MNLE: a custom combined_embedding_net is not implemented; the built-in "
+                                      "two-layer ReLU MLP (combined_embedding_features) runs on the kernels")
+
+    def build(self, batch_input: Tensor, batch_condition: Tensor):
+        from sbi_amd.neural_nets.net_builders.mixed_nets import _build_mixed_density_estimator
+
+        return _build_mixed_density_estimator(
+            batch_x=batch_input, batch_y=batch_condition, continuous_config=self.continuous,
+            z_score_y=self.z_score_condition, num_categories_per_variable=self.num_categories_per_variable,
+            embedding_net=nn.Identity() if self.embedding_net is None else self.embedding_net,
+            combined_embedding_net=self.combined_embedding_net, log_transform_x=self.log_transform_x,
+            discrete_hidden_features=self.discrete_hidden_features,
+            discrete_hidden_layers=self.discrete_hidden_layers,
+            combined_embedding_features=self.combined_embedding_features,
+            dropout_probability=self.dropout_probability)
+
+
 @dataclass(frozen=True)
 class ResNetClassifierConfig:
     """sbi's ``ResNetClassifierConfig`` (estimator_configs.py:1397-1411): the residual-network ratio classifier of NRE
