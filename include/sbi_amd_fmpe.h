@@ -92,7 +92,8 @@ int sbi_amd_fmpe_loss_fwd_bwd(const sbi_amd_fmpe_config* cfg, const float* param
  *   sbi_amd_fmpe_velocity as its 1-element `times` for stage i+1);  slot 23: current t;  slot 24: 1.0 once t has
  *   reached t1 (the only value the host ever reads; an attempt after that is a no-op);  slots 25/26: accepted /
  *   rejected attempts;  slot 27: last error ratio;  slot 28: 1.0 if the current attempt reaches t1 when accepted.
- *   Slots 0..15 are the controller's doubles.
+ *   Slots 0..15 are the controller's doubles.  The no-op attempt after the end (h = 0, so y5 = y and k7 = k1) leaves
+ *   y, k1, t, h and both flags as they are and counts as neither accepted nor rejected: slots 25/26 stay.
  * One attempt = for i = 1..6 { sbi_amd_dopri5_stage(i) -> y_stage; k[i] = velocity(y_stage, time slot 16+i) };
  * sbi_amd_dopri5_finish (y5 = the stage-6 state; on acceptance y <- y5 and k[0] <- k[6] in place).
  * k: HOST array of 7 DEVICE pointers k1..k7 (n floats each), n = rows x D. scratch: 256 doubles (device). */

@@ -143,7 +143,8 @@ __global__ void __launch_bounds__(256) dopri5_control_kernel(float* __restrict__
     double* d = reinterpret_cast<double*>(st);
     const double hs = d[7];
     const double hh = hs < 0 ? -hs : hs;
-    if (accept) { d[0] += hs; st[ST_ACC] += 1.f; } else { st[ST_REJ] += 1.f; }
+    if (accept) d[0] += hs;
+    if (hh > 0.0) st[accept ? ST_ACC : ST_REJ] += 1.f;      // (a no-op attempt after the end counts as neither)
     double factor;
     if (!(ratio == ratio)) factor = 0.2;
     else if (ratio <= 0.0) factor = 5.0;

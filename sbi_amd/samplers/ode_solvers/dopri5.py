@@ -185,6 +185,9 @@ def _odeint_host(f, y0: Tensor, t0: float, t1: float, atol: float, rtol: float, 
             t += hs
             y = y5
             k1 = ks[6]
-        factor = 0.9 * ratio ** (-0.2) if ratio > 0.0 else 5.0
+        if ratio != ratio:                        # NaN: rejected above; shrink, as the device controller does
+            factor = 0.2
+        else:
+            factor = 0.9 * ratio ** (-0.2) if ratio > 0.0 else 5.0
         h *= min(5.0, max(0.2, factor))
     raise RuntimeError("odeint_dopri5: max_steps exceeded")

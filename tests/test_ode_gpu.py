@@ -1,5 +1,9 @@
 """The device-resident Dormand-Prince stepper (csrc/ode.hip behind sbi_amd_dopri5_*) against the same method with a
-host-side controller (torch ops) and against a tight fp64 solve, on right-hand sides with known behaviour."""
+host-side controller (torch ops) and against a tight fp64 solve, on right-hand sides with known behaviour.
+
+An adaptive solve corrects for most mistakes in the parts that do the adapting, so these whole solves say little about
+them: the kernels are checked one attempt at a time (tableau and error coefficients, scale, decision, state block,
+grid-stride wraps, refusals) in tests/test_ode_step_gpu.py, against the restatement of tests/ode_restatement.py."""
 
 import pytest
 import torch
