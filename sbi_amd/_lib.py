@@ -49,6 +49,12 @@ class MAFConfigC(Structure):
     ]
 
 
+class MAFAffineConfigC(Structure):
+    """Mirror of ``struct sbi_amd_maf_affine_config`` (include/sbi_amd_maf_affine.h)."""
+
+    _fields_ = [("D", c_int32), ("C", c_int32), ("H", c_int32), ("T", c_int32), ("NB", c_int32), ("epsilon", c_float)]
+
+
 class MDNConfigC(Structure):
     """Mirror of ``struct sbi_amd_mdn_config`` (include/sbi_amd_mdn.h)."""
 
@@ -372,9 +378,32 @@ _SIGNATURES_MNLE = {
          c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+_AFFP = POINTER(MAFAffineConfigC)
+_SIGNATURES_MAF_AFFINE = {
+    "sbi_amd_maf_affine_param_count": (c_int64, [_AFFP]),
+    "sbi_amd_maf_affine_packed_floats": (c_int64, [_AFFP]),
+    "sbi_amd_maf_affine_param_offset": (c_int64, [_AFFP, c_int32, c_int32, c_int32]),
+    "sbi_amd_maf_affine_pack": (c_int, [_AFFP, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_maf_affine_log_prob": (
+        c_int, [_AFFP, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_maf_affine_sample": (
+        c_int, [_AFFP, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_maf_affine_train_workspace_floats": (c_int64, [_AFFP, c_int64]),
+    "sbi_amd_maf_affine_loss_fwd_bwd": (
+        c_int,
+        [_AFFP, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_maf_affine_log_prob_trials": (
+        c_int, [_AFFP, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+}
+
 
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+def exported_symbols_maf_affine():
+    return list(_SIGNATURES_MAF_AFFINE)
 
 
 def exported_symbols_mnle():
@@ -438,7 +467,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                            "`python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
-                                      **_SIGNATURES_MNLE}.items():
+                                      **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

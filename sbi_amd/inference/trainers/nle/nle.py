@@ -22,7 +22,7 @@ from sbi_amd.inference.trainers.npe.npe import (ImproperEmpirical, PosteriorEsti
                                                 validate_theta_and_x)
 from sbi_amd.neural_nets.estimators.base import ConditionalDensityEstimator
 from sbi_amd.neural_nets.factory import likelihood_nn
-from sbi_amd.neural_nets.net_builders.estimator_configs import NSFConfig, ZukoNSFConfig
+from sbi_amd.neural_nets.net_builders.estimator_configs import MAFConfig, NSFConfig, ZukoNSFConfig
 from sbi_amd.utils.sbiutils import handle_invalid_x, mcmc_transform, warn_on_invalid_x
 from sbi_amd.utils.torchutils import check_if_prior_on_device
 
@@ -46,7 +46,7 @@ class NLE_A(PosteriorEstimatorTrainer):
         # every builder is called as build(batch_theta, batch_x) and returns q(x | theta) (nle_base.py:413-444)
         if isinstance(density_estimator, str):
             self._build_neural_net = likelihood_nn(model=density_estimator)
-        elif isinstance(density_estimator, NSFConfig):
+        elif isinstance(density_estimator, (NSFConfig, MAFConfig)):
             cfg = density_estimator
             self._build_neural_net = lambda batch_theta, batch_x: cfg.build(batch_x, batch_theta)
         else:

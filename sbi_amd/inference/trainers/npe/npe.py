@@ -30,9 +30,9 @@ from torch import Tensor, nn
 from torch.distributions import Distribution
 
 from sbi_amd.neural_nets.estimators.base import ConditionalDensityEstimator
-from sbi_amd.neural_nets.estimators.nsf_flow import NSFFlow
+from sbi_amd.neural_nets.estimators.nsf_flow import NSFFlow, NSFNet
 from sbi_amd.neural_nets.factory import posterior_nn
-from sbi_amd.neural_nets.net_builders.estimator_configs import MDNConfig, NSFConfig, ZukoNSFConfig
+from sbi_amd.neural_nets.net_builders.estimator_configs import MAFConfig, MDNConfig, NSFConfig, ZukoNSFConfig
 from sbi_amd.utils.collectives import all_reduce_sum
 from sbi_amd.utils.sbiutils import handle_invalid_x, warn_on_invalid_x
 from sbi_amd.utils.torchutils import check_if_prior_on_device, process_device
@@ -74,7 +74,7 @@ def check_estimator_arg(estimator) -> None:
         )
     if isinstance(estimator, type):
         raise TypeError("Pass a config *instance* (e.g. NSFConfig()), not the config class.")
-    if not (isinstance(estimator, (str, NSFConfig, ZukoNSFConfig, MDNConfig)) or callable(estimator)):
+    if not (isinstance(estimator, (str, NSFConfig, ZukoNSFConfig, MDNConfig, MAFConfig)) or callable(estimator)):
         raise TypeError(f"Unsupported density_estimator argument of type {type(estimator).__name__}")
 
 
@@ -129,7 +129,7 @@ class PosteriorEstimatorTrainer:
                 "`from sbi_amd.neural_nets import NSFConfig`.", FutureWarning, stacklevel=3,
             )
             self._build_neural_net = posterior_nn(model=density_estimator)
-        elif isinstance(density_estimator, (NSFConfig, ZukoNSFConfig, MDNConfig)):
+        elif isinstance(density_estimator, (NSFConfig, ZukoNSFConfig, MDNConfig, MAFConfig)):
             self._build_neural_net = density_estimator.build
         else:
             self._build_neural_net = density_estimator
@@ -373,6 +373,11 @@ class PosteriorEstimatorTrainer:
             raise TypeError(f"{type(self).__name__} cannot train {type(net).__name__}: it has no trainable "
                             "parameters.")
         d = self._dist()
+        from sbi_amd.neural_nets.estimators.maf_affine_flow import MAFFlow
+
+        if d is not None and isinstance(net, MAFFlow):
+            raise NotImplementedError("sbi_amd: multi-GPU training of the affine MAF is not implemented; train it on "
+                                      "one device, or use NSFConfig(), which trains data-parallel")
         if d is not None:   # replicas start identical
             for p in list(net.parameters()) + list(net.buffers()):
                 p.data.copy_(self._bcast(p.data))
@@ -499,8 +504,9 @@ class PosteriorEstimatorTrainer:
             return batch_losses(my_slice(val_epoch_idx[b * Bv : (b + 1) * Bv]), False, Bv)
 
         snap_ring = [None] * 4       # (at most three epoch records are alive at a time)
-        if (fused and not atomic and n_train_batches <= 2 and isinstance(net, NSFFlow) and hasattr(net.net, "hyper")
-                and not isinstance(net, MixtureDensityEstimator) and _os.environ.get("SBI_AMD_TAIL_EXTRA", "1") != "0"):
+        if (fused and not atomic and n_train_batches <= 2 and isinstance(net, NSFFlow)
+                and isinstance(net.net, NSFNet)      # (the query is the NSF kernels'; other families have one image)
+                and _os.environ.get("SBI_AMD_TAIL_EXTRA", "1") != "0"):
             # one or two steps per epoch, validation batches on the OTHER kernel family (e.g. batch 65 536 / 10 000
             # validation rows): let the step's table pack refresh the validation image too instead of a separate pack
             # launch every epoch

@@ -1,5 +1,7 @@
 from sbi_amd.neural_nets.factory import (build_score_matching_estimator, classifier_nn, likelihood_nn,  # noqa: F401
                                           posterior_flow_nn, posterior_nn, posterior_score_nn)
-from sbi_amd.neural_nets.net_builders.estimator_configs import (MAFRQSConfig, MDNConfig, MixedConfig,  # noqa: F401
+from sbi_amd.neural_nets.net_builders.estimator_configs import (MAFConfig, MAFRQSConfig, MDNConfig,  # noqa: F401
+                                                                MixedConfig,
                                                                 NSFConfig,
                                                                 ResNetClassifierConfig, ZukoNSFConfig)
+from sbi_amd.neural_nets.net_builders.flow import build_maf  # noqa: F401,E402

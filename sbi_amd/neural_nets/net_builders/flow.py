@@ -178,6 +178,47 @@ def build_maf_rqs(
     return MAFRQSFlow(net, input_shape=batch_x[0].shape, condition_shape=batch_y[0].shape, embedding_net=embedding)
 
 
+def build_maf(
+    batch_x: Tensor,
+    batch_y: Tensor,
+    z_score_x: Optional[str] = "independent",
+    z_score_y: Optional[str] = "independent",
+    hidden_features: int = 50,
+    num_transforms: int = 5,
+    embedding_net: nn.Module = nn.Identity(),
+    num_blocks: int = 2,
+    dropout_probability: float = 0.0,
+    use_batch_norm: bool = False,
+    **kwargs,
+):
+    """Same signature and meaning as the reference ``build_maf`` (flow.py:115-209), sbi's default density estimator:
+    num_transforms x [MaskedAffineAutoregressiveTransform(hidden_features, num_blocks feed-forward blocks, tanh),
+    RandomPermutation], z-scoring of both sides.  Runs on the affine MAF HIP kernels
+    (include/sbi_amd_maf_affine.h); unsupported options raise instead of degrading, unrelated kwargs are ignored."""
+    from sbi_amd.neural_nets.estimators.maf_affine_flow import MAFAffineHyper, MAFAffineNet, MAFFlow
+
+    check_data_device(batch_x, batch_y)
+    assert_transform_to_unconstrained_supported(
+        z_score_x, "build_maf",
+        "Use one of 'none', 'independent', 'structured'.",
+    )
+    if dropout_probability != 0.0:
+        raise NotImplementedError("sbi_amd.build_maf: dropout is not implemented in the HIP path; use "
+                                  "dropout_probability=0.0")
+    if use_batch_norm:
+        raise NotImplementedError("sbi_amd.build_maf: batch norm is not implemented in the HIP path; use "
+                                  "use_batch_norm=False (sbi's recommendation)")
+    if batch_x[0].numel() == 1:
+        import warnings
+
+        warnings.warn("In one-dimensional output space, this flow is limited to Gaussians", stacklevel=2)
+    D, C, zstats, zx, zy, embedding = _flow_inputs(batch_x, batch_y, z_score_x, z_score_y, embedding_net, "build_maf")
+    hyper = MAFAffineHyper(D=D, C=C, hidden_features=hidden_features, num_transforms=num_transforms,
+                           num_blocks=num_blocks)
+    net = MAFAffineNet(hyper, zstats, z_score_theta=zx, z_score_x=zy, dtype=kwargs.get("dtype", torch.float32))
+    return MAFFlow(net, input_shape=batch_x[0].shape, condition_shape=batch_y[0].shape, embedding_net=embedding)
+
+
 def build_zuko_nsf(
     batch_x: Tensor,
     batch_y: Tensor,
