@@ -15,7 +15,7 @@ import torch
 from sbi_amd import _build
 
 _LIB: Optional[ctypes.CDLL] = None
-ABI_VERSION = 117    # must equal sbi_amd_nsf_abi_version() (csrc/nsf_plan.cpp) and SBI_AMD_NSF_ABI_VERSION (include/)
+ABI_VERSION = 118    # must equal sbi_amd_nsf_abi_version() (csrc/nsf_plan.cpp) and SBI_AMD_NSF_ABI_VERSION (include/)
 
 E_UNSUPPORTED, E_BADARG, E_LDS = -1, -2, -3
 _ERRORS = {
@@ -397,9 +397,21 @@ _SIGNATURES_MAF_AFFINE = {
         c_int, [_AFFP, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_sir.h (the selection step of sampling-importance-resampling)
+_SIGNATURES_SIR = {
+    "sbi_amd_sir_resample": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p]),
+}
+
 
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+def exported_symbols_sir():
+    return list(_SIGNATURES_SIR)
 
 
 def exported_symbols_maf_affine():
@@ -467,7 +479,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                            "`python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
-                                      **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE}.items():
+                                      **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

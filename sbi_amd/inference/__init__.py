@@ -1,4 +1,5 @@
 from sbi_amd.inference.posteriors.direct_posterior import DirectPosterior  # noqa: F401
+from sbi_amd.inference.posteriors.importance_posterior import ImportanceSamplingPosterior  # noqa: F401
 from sbi_amd.inference.posteriors.mcmc_posterior import MCMCPosterior  # noqa: F401
 from sbi_amd.inference.posteriors.rejection_posterior import RejectionPosterior  # noqa: F401
 from sbi_amd.inference.trainers.nle.mnle import MNLE  # noqa: F401

@@ -189,7 +189,8 @@ class PosteriorEstimatorTrainer:
         else:
             warn_on_invalid_x(num_nans, num_infs, exclude_invalid_x)
         x, theta = x[is_valid_x], theta[is_valid_x]
-        self._check_proposal(proposal)
+        if not restricted_prior:      # (a truncated prior is round-0 data: the atomic-loss warning would be wrong)
+            self._check_proposal(proposal)
         self._data_round_index.append(current_round)
         self._theta_roundwise.append(theta)
         self._x_roundwise.append(x)

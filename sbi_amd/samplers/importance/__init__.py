@@ -1,0 +1,2 @@
+from sbi_amd.samplers.importance.importance_sampling import importance_sample  # noqa: F401
+from sbi_amd.samplers.importance.sir import sampling_importance_resampling, sir_select  # noqa: F401
