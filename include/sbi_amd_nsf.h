@@ -429,7 +429,7 @@ int sbi_amd_nre_mcmc_slice_run(const sbi_amd_nre_config* cfg, const float* packe
                                void* stream);
 
 /* Library/ABI version (major*100 + minor) and the gfx arch string it was built for. */
-#define SBI_AMD_NSF_ABI_VERSION 118
+#define SBI_AMD_NSF_ABI_VERSION 119
 int sbi_amd_nsf_abi_version(void);
 const char* sbi_amd_nsf_arch(void);
 

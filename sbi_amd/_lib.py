@@ -15,7 +15,7 @@ import torch
 from sbi_amd import _build
 
 _LIB: Optional[ctypes.CDLL] = None
-ABI_VERSION = 118    # must equal sbi_amd_nsf_abi_version() (csrc/nsf_plan.cpp) and SBI_AMD_NSF_ABI_VERSION (include/)
+ABI_VERSION = 119    # must equal sbi_amd_nsf_abi_version() (csrc/nsf_plan.cpp) and SBI_AMD_NSF_ABI_VERSION (include/)
 
 E_UNSUPPORTED, E_BADARG, E_LDS = -1, -2, -3
 _ERRORS = {
@@ -405,9 +405,21 @@ _SIGNATURES_SIR = {
          c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_mmd.h (RBF-kernel two-sample sums: the misspecification test's permutation baseline, the MMD metrics)
+_SIGNATURES_MMD = {
+    "sbi_amd_mmd_rbf_splits": (
+        c_int,
+        [c_void_p, c_int64, c_int32, c_void_p, c_uint64, c_uint64, c_int64, c_int32, c_int32, c_int32, c_int32,
+         c_void_p, c_float, c_void_p, c_void_p]),
+}
+
 
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+def exported_symbols_mmd():
+    return list(_SIGNATURES_MMD)
 
 
 def exported_symbols_sir():
@@ -479,7 +491,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                            "`python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
-                                      **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR}.items():
+                                      **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
+                                      **_SIGNATURES_MMD}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes
