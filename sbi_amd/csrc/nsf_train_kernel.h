@@ -743,6 +743,133 @@ __device__ __forceinline__ void write_bias(float* __restrict__ part, const LinDe
   }
 }
 
+// ---- the same write-out for the static default layout (SP instantiations): the layout is constexpr and the grad wave
+// index GW a template argument (the kernel dispatches once per transform on the wave-uniform index), so every guard of
+// write_tile / write_thin that the layout decides folds away, every slab offset is one per-lane base plus an immediate,
+// and what stays run-time -- the bias column, the dead columns past it, the rows past a layer's last -- is ONE lane
+// predicate per register group, with the bias word reached through a selected (offset, stride) instead of a second
+// branch.  Same words, same values, same addresses as the guarded code above.
+constexpr LinDesc wo_lin(int i) { return kStaticPl.shape[0].lin[i]; }
+// offset and register stride of lane (g, j)'s words of rows row0 + 4 g + r, input column `in` (in == L.in: the bias)
+#define WO_LANE_WORDS(L, row0, in)                                    \
+  const bool wcol_ = (in) < (L).in;                                   \
+  const int off = wcol_ ? (L).g_w + ((row0) + 4 * g) * (L).in + (in) : (L).g_b + (row0) + 4 * g; \
+  const int stride = wcol_ ? (L).in : 1;
+// m-tile GW, n-tiles [0, NT) of layer LI (accumulator nt = n-tile nt)
+template <int LI, int GW, int NT>
+__device__ __forceinline__ void wo_tiles(float* __restrict__ part, int j, int g, const f4* acc) {
+  constexpr LinDesc L = wo_lin(LI);
+  constexpr int rem = L.out - 16 * GW;             // live rows of the m-tile
+  static_assert(rem >= 16 || (rem > 0 && rem <= 4), "a partial m-tile's live rows sit in lane group 0");
+  constexpr int RL = rem >= 16 ? 4 : rem;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    if (16 * nt > L.in) continue;                  // (compile time: past the bias column)
+    const int in = 16 * nt + j;
+    WO_LANE_WORDS(L, 16 * GW, in)
+    bool live = in <= L.in;                        // folds for the n-tiles left of the bias column
+    if (rem < 16) live = live && g == 0;
+    if (live) {
+#pragma unroll
+      for (int r = 0; r < RL; ++r) part[off + r * stride] = acc[nt][r];
+    }
+  }
+}
+// grad wave 3's thin strips of hidden layer LI (see dw_thin, write_thin)
+template <int LI>
+__device__ __forceinline__ void wo_thin(float* __restrict__ part, int l, const f4& accM, const f4& accN) {
+  constexpr LinDesc L = wo_lin(LI);
+  static_assert(L.out == TR_THIN_C0 + 2 && L.in == L.out, "thin strips: a 50 x 50 hidden layer");
+  if (l <= L.in) {                                 // M-strip: rows 48, 49 x column l
+    const bool w = l < L.in;
+    const int off = w ? L.g_w + TR_THIN_C0 * L.in + l : L.g_b + TR_THIN_C0;
+    const int stride = w ? L.in : 1;
+#pragma unroll
+    for (int m = 0; m < L.out - TR_THIN_C0; ++m) part[off + m * stride] = accM[m];
+  }
+  const int in = TR_THIN_C0 + (l & 3);
+  if (l < TR_THIN_C0 && in <= L.in) {              // N-strips: rows 4 (l >> 2) + m x column 48 + (l & 3)
+    const bool w = in < L.in;
+    const int row = 4 * (l >> 2);
+    const int off = w ? L.g_w + row * L.in + in : L.g_b + row;
+    const int stride = w ? L.in : 1;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) part[off + m * stride] = accN[m];
+  }
+}
+// final layer: parameter tile PTI of transformed dim DD, n-tiles [NT0, NT0 + NTN) (accumulator i = n-tile NT0 + i)
+template <int DD, int PTI, int NT0, int NTN>
+__device__ __forceinline__ void wo_final(float* __restrict__ part, int j, int g, const f4* acc) {
+  constexpr LinDesc L = wo_lin(kStaticPl.shape[0].fin);
+  constexpr int P = kStaticPl.P;
+  constexpr int rem = P - 16 * PTI;                // live parameters of the tile: lane groups < GF hold four, group GF
+  static_assert(rem > 0, "parameter tile");        // holds RP, the groups above none
+  constexpr int GF = rem / 4, RP = rem % 4;
+#pragma unroll
+  for (int i = 0; i < NTN; ++i) {
+    if (16 * (NT0 + i) > L.in) continue;           // (compile time)
+    const int in = 16 * (NT0 + i) + j;
+    WO_LANE_WORDS(L, DD * P + 16 * PTI, in)
+    const bool live = in <= L.in;
+    if (live && g <= GF) {
+#pragma unroll
+      for (int r = 0; r < RP; ++r) part[off + r * stride] = acc[i][r];
+    }
+    if (live && g < GF) {
+#pragma unroll
+      for (int r = RP; r < 4; ++r) part[off + r * stride] = acc[i][r];
+    }
+  }
+}
+// LULinear block: wave 0 holds d U (+ the logabsdet slot), wave 1 d L and the bias
+template <int GW>
+__device__ __forceinline__ void wo_lu(float* __restrict__ part, int j, int g, const f4& acc) {
+  constexpr int D = kStaticPl.D, ntri = D * (D - 1) / 2;
+  constexpr int o_low = kStaticPl.shape[0].g_lu, o_up = o_low + ntri, o_diag = o_up + ntri, o_bias = o_diag + D;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = 4 * g + r, k = j;
+    if (GW == 0) {
+      const bool tri = i < D && k < D && k >= i, lad = i == D && k == D;
+      const int off = lad ? kStaticPl.shape[0].n_params
+                          : (k > i ? o_up + i * D - i * (i + 1) / 2 + (k - i - 1) : o_diag + i);
+      if (tri || lad) part[off] = acc[r];
+    } else {
+      const bool low = i < D && k < i, bias = i < D && k == D;
+      const int off = bias ? o_bias + i : o_low + i * (i - 1) / 2 + k;
+      if (low || bias) part[off] = acc[r];
+    }
+  }
+}
+#undef WO_LANE_WORDS
+// one grad wave's whole write-out
+template <int GW>
+__device__ __forceinline__ void wo_static(float* __restrict__ part, int j, int g, int l, const f4 (&acc0)[1],
+                                          const f4 (&accC)[2][1], const f4 (&acc1)[2][4], const f4 (&acc2)[2][4],
+                                          const f4 (&accF)[3][4], const f4& accLU) {
+  constexpr int PT = kStaticPl.PT, d_tr = kStaticPl.shape[0].d_tr;
+  static_assert(kStaticPl.NB == 2 && PT == 2 && kStaticTp.nch[0] == 3 && (d_tr & 1) && d_tr == 5 && TR_NW == 4,
+                "chunks of two dims, the last one split (see the chunk steps)");
+  wo_tiles<0, GW, 1>(part, j, g, acc0);
+  wo_tiles<1, GW, 1>(part, j, g, accC[0]);
+  wo_tiles<4, GW, 1>(part, j, g, accC[1]);
+  if constexpr (GW == TR_NW - 1) {
+    wo_thin<2>(part, l, acc1[0][0], acc1[0][1]);
+    wo_thin<3>(part, l, acc2[0][0], acc2[0][1]);
+    wo_thin<5>(part, l, acc1[1][0], acc1[1][1]);
+    wo_thin<6>(part, l, acc2[1][0], acc2[1][1]);
+  } else {                                         // (n-tile 3 is in wave 3's N-strips)
+    wo_tiles<2, GW, 3>(part, j, g, acc1[0]);
+    wo_tiles<3, GW, 3>(part, j, g, acc2[0]);
+    wo_tiles<5, GW, 3>(part, j, g, acc1[1]);
+    wo_tiles<6, GW, 3>(part, j, g, acc2[1]);
+  }
+  wo_final<0 + GW / PT, GW % PT, 0, 4>(part, j, g, accF[0]);
+  wo_final<2 + GW / PT, GW % PT, 0, 4>(part, j, g, accF[1]);
+  wo_final<4, GW % PT, PT * (GW / PT), PT>(part, j, g, accF[2]);   // the split last chunk
+  if constexpr (GW < 2) wo_lu<GW>(part, j, g, accLU);
+}
+
 // ------------------------------------------------------------------ backward kernel
 __device__ __forceinline__ constexpr int cm_reps(const NsfPlan& pl) { return pl.ctx_reps; }   // (0: no hidden layer)
 // Wave specialisation, one workgroup = 64-row tile:
@@ -807,7 +934,14 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
 #define NSF_ABLV (pl_.ablate)
 #define TS(i) do { if (dbg && t == 0 && blockIdx.x == 0 && (threadIdx.x & 63) == 0 && tile == (int)(blockIdx.x + (dbg_tile_sel ? gridDim.x : 0))) \
     dbg[(threadIdx.x >> 6) * 64 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
+  // transform-boundary stamps of workgroup 0, one row of 8 per wave and transform (second half of the 1024-word buffer):
+  //   0/1 grad waves: partial-gradient write-out begins / its last store is issued
+  //   2/3 row waves: stage_layer of the next transform's image begins / ends
+  //   4/5 both: arrival at / release from S0 of the transform's first tile
+#define TSX(i) do { if (dbg && t < 8 && blockIdx.x == 0 && (threadIdx.x & 63) == 0) \
+    dbg[512 + (threadIdx.x >> 6) * 64 + 8 * t + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
 #else
+#define TSX(i) do { } while (0)
 #define NSF_ABL(bit) 0
 #define NSF_ABLV 0
 #define TS(i) do { } while (0)
@@ -928,7 +1062,7 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
       // barrier at all: after Y2 it touches only its own scratch rows and Bs (whose readers finished before Y2), and the
       // shared tiles are next written by the grad waves, who rendezvous among themselves (TR_NO_S0).
       const bool need_s0 = !TR_NO_S0 || ov || tile == (int)blockIdx.x;
-      if (need_s0) __syncthreads();
+      if (need_s0) { TSX(4); __syncthreads(); TSX(5); }
       if (ov) {
         stage_layer(lds, img + F0, pl.lds_w_train_floats - F0, tid, blockDim.x);
         __syncthreads();
@@ -1219,7 +1353,9 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
     }
     // the next transform's weight image (nobody reads the old one after the last tile's Y2; the grad waves are busy
     // writing their partial gradients meanwhile; the S0 barrier of the next tile publishes it)
+    TSX(2);
     if (t > io.t_lo && !ov) stage_layer(lds, packed + (long long)(t - 1) * pl.img_floats, pl.lds_w_train_floats, tid, 64 * TR_NW);
+    TSX(3);
     }   // transforms
 
   } else {
@@ -1301,7 +1437,7 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
       const int t_nxt = more_tiles ? t : (t > io.t_lo ? t - 1 : t);
       const int tile_nxt = more_tiles ? tile + (int)gridDim.x : (t > io.t_lo ? (int)blockIdx.x : tile);
       const bool need_s0 = !TR_NO_S0 || ov || tile == (int)blockIdx.x;
-      if (need_s0) __syncthreads();                // S0
+      if (need_s0) { TSX(4); __syncthreads(); TSX(5); }   // S0
       else { sync_target += 4; grad_wave_sync(cnt, sync_target, id.lane); }   // every d LU read of the previous tile is done
       if (ov) {
         stage_layer(lds, img + F0, pl.lds_w_train_floats - F0, tid, blockDim.x);
@@ -1414,7 +1550,19 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
     }
 
     // ---- write this workgroup's partial gradients (natural parameter order)
+    TSX(0);
     float* part = partial + ((long long)t * gridDim.x + blockIdx.x) * tp.PLP;
+    if constexpr (SP != 0) {
+      // static layout: one dispatch on the wave index, then straight-line stores (wo_static); the laundered lane
+      // coordinates get their ranges back so that the guards they decide fold
+      const int j = id.j & 15, g = id.g & 3, l = id.lane & 63;
+      switch (__builtin_amdgcn_readfirstlane(gw)) {
+        case 0: wo_static<0>(part, j, g, l, acc0, accC, acc1, acc2, accF, accLU[0]); break;
+        case 1: wo_static<1>(part, j, g, l, acc0, accC, acc1, acc2, accF, accLU[0]); break;
+        case 2: wo_static<2>(part, j, g, l, acc0, accC, acc1, acc2, accF, accLU[0]); break;
+        default: wo_static<3>(part, j, g, l, acc0, accC, acc1, acc2, accF, accLU[0]); break;
+      }
+    } else {
     const int out0 = 16 * gw;
   #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) write_tile(part, L0, out0, nt, id, acc0[nt]);
@@ -1504,6 +1652,8 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
         }
       }
     }
+    }
+    TSX(1);
     }   // transforms
 
   }
@@ -1511,6 +1661,7 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
 #undef NSF_ABL
 #undef NSF_ABLV
 #undef TS
+#undef TSX
 }
 
 
