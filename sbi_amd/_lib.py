@@ -413,6 +413,18 @@ _SIGNATURES_MMD = {
          c_void_p, c_float, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_abc.h (ABC: the pairwise mixture log-sum-exp of the SMC weights / the KDE, the persistent Sinkhorn)
+_SIGNATURES_ABC = {
+    "sbi_amd_mixture_lse": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+         c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_sinkhorn": (
+        c_int,
+        [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_float,
+         c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 
 def exported_symbols():
     return list(_SIGNATURES)
@@ -420,6 +432,10 @@ def exported_symbols():
 
 def exported_symbols_mmd():
     return list(_SIGNATURES_MMD)
+
+
+def exported_symbols_abc():
+    return list(_SIGNATURES_ABC)
 
 
 def exported_symbols_sir():
@@ -492,7 +508,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     lib = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
-                                      **_SIGNATURES_MMD}.items():
+                                      **_SIGNATURES_MMD, **_SIGNATURES_ABC}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

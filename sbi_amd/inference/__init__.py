@@ -9,3 +9,4 @@ from sbi_amd.inference.trainers.nre.nre import (AALR, BNRE, CNRE, NRE, NRE_A, NR
                                                 SNRE_B, SNRE_C, SRE)
 from sbi_amd.inference.trainers.vfpe.fmpe import FMPE, posterior_flow_nn  # noqa: F401
 from sbi_amd.inference.trainers.vfpe.npse import NPSE, posterior_score_nn  # noqa: F401
+from sbi_amd.inference.abc import MCABC, SMCABC  # noqa: F401

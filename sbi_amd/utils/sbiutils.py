@@ -241,3 +241,24 @@ def gradient_ascent(potential_fn: Callable, inits: Tensor, theta_transform=None,
     except KeyboardInterrupt:
         print(f"Optimization was interrupted after {done} iterations. " + interruption_note)
     return incumbent.theta, incumbent.value
+
+
+def process_x(x, x_event_shape: Optional[torch.Size] = None) -> Tensor:
+    """The observation as a float32 tensor with a leading batch dimension (sbi/utils/user_input_checks.py `process_x`,
+    as far as the ABC samplers need it): an `x` of the event shape gets a batch of 1; a batch of iid observations is
+    kept.  A shape that matches neither raises."""
+    x = torch.atleast_1d(torch.as_tensor(x, dtype=torch.float32))
+    if x_event_shape is None:
+        return x if x.dim() > 1 else x.unsqueeze(0)
+    x_event_shape = torch.Size(x_event_shape)
+    if x.shape == x_event_shape:
+        return x.unsqueeze(0)
+    if x.shape[1:] == x_event_shape:
+        return x
+    raise ValueError(f"Observed data shape ({tuple(x.shape[1:])}) must match the shape of simulated data x "
+                     f"({tuple(x_event_shape)}).")
+
+
+def assert_all_finite(quantity: Tensor, description: str = "tensor") -> None:
+    """Raise if the tensor holds a NaN or an infinity."""
+    assert torch.isfinite(quantity).all(), f"NaN/Inf present in {description}."
