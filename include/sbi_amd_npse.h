@@ -15,6 +15,9 @@
  *   sbi_amd_npse_sample_sde      Diffuser.run with the euler_maruyama predictor and no corrector
  *                                samplers/score/diffuser.py:124-172, samplers/score/predictors.py:112-120
  *
+ * N iid observations (the fnpe / gauss / auto_gauss score composition and its sampler) have a header of their own:
+ * include/sbi_amd_npse_iid.h.
+ *
  * SDE families (mean_t_fn m(t), std_fn s(t), drift f(theta, t), diffusion g(t); score_estimator.py:582-641, 695-769,
  * 905-975), with B = beta_max - beta_min, beta(t) = beta_min + B t, sigma(t) = sigma_min (sigma_max / sigma_min)^t:
  *   0 ve     m = 1                                   s = sigma(t)           f = 0                 g = sigma(t) sqrt(2 ln(sigma_max / sigma_min))

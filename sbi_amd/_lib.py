@@ -309,6 +309,25 @@ _SIGNATURES_NPSE = {
 }
 
 
+# include/sbi_amd_npse_iid.h (NPSE with iid observations: the composed score and its sampler)
+_SIGNATURES_NPSE_IID = {
+    "sbi_amd_npse_iid_workspace_floats": (c_int64, [POINTER(NPSEConfigC), c_int64]),
+    "sbi_amd_npse_score_iid": (
+        c_int,
+        [POINTER(NPSEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+    "sbi_amd_npse_compose_iid": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                         c_void_p, c_void_p]),
+    "sbi_amd_npse_sde_normals": (c_int, [c_uint64, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p]),
+    "sbi_amd_npse_sample_sde_iid": (
+        c_int,
+        [POINTER(NPSEConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_float, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_uint64, c_int64, c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+}
+
+
 # include/sbi_amd_lc2st.h (the L-C2ST classifier ensemble; `exported_symbols_lc2st()` is what its header is checked against)
 _SIGNATURES_LC2ST = {
     "sbi_amd_lc2st_param_count": (c_int64, [POINTER(LC2STConfigC)]),
@@ -462,6 +481,10 @@ def exported_symbols_npse():
     return list(_SIGNATURES_NPSE)
 
 
+def exported_symbols_npse_iid():
+    return list(_SIGNATURES_NPSE_IID)
+
+
 def load(build_if_missing: bool = True) -> ctypes.CDLL:
     """Load libsbi_amd_nsf.so (building it in-tree with hipcc if needed)."""
     global _LIB
@@ -506,7 +529,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
         raise RuntimeError(f"{path} is stale (built from different sources); rebuild it with "
                            "`python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(str(path))
-    for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
+    for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_NPSE_IID, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
                                       **_SIGNATURES_MMD, **_SIGNATURES_ABC}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it

@@ -13,6 +13,8 @@
 // the control variate off (threshold <= 0) a wave holds 16 rows as on the FMPE path.
 #include "fmpe_kernel.h"
 #include "../../include/sbi_amd_npse.h"
+#include "../../include/sbi_amd_npse_iid.h"
+#include "npse_iid_kernel.h"
 
 namespace {
 
@@ -128,6 +130,92 @@ int sbi_amd_npse_sample_sde(const sbi_amd_npse_config* cfg, const float* packed,
   a.steps = steps; a.eta = eta; a.base = base; a.sde_noise = noise; a.seed = seed; a.row_offset = row_offset;
   a.v_out = theta_out; a.ntiles = (int)((n + FM_ROWS - 1) / FM_ROWS);
   return fm_launch_fwd<6>(pl, a, (hipStream_t)stream);
+}
+
+// ---- iid observations: the composed score and its sampler (npse_iid_kernel.h)
+static int np_iid_envelope(const FmPlan& pl, int64_t N) {
+  return (pl.D <= NP_IID_MAX_D && N >= 1 && N <= NP_IID_MAX_N) ? 0 : SBI_AMD_E_UNSUPPORTED;
+}
+
+int64_t sbi_amd_npse_iid_workspace_floats(const sbi_amd_npse_config* cfg, int64_t N) {
+  FmPlan pl;
+  int rc = np_build_plan(cfg, &pl);
+  if (rc) return rc;
+  if (N < 1) return SBI_AMD_E_BADARG;
+  rc = np_iid_envelope(pl, N);
+  if (rc) return rc;
+  return N * NP_IID_EC;
+}
+
+int sbi_amd_npse_score_iid(const sbi_amd_npse_config* cfg, const float* packed, const float* zstats,
+                           const float* theta_t, const float* x, int64_t N, const float* time, const float* lam,
+                           const float* mats, const float* vec, int64_t n, float* workspace, float* out, void* stream) {
+  FmPlan pl;
+  int rc = np_build_plan(cfg, &pl);
+  if (rc) return rc;
+  if (!packed || !zstats || !theta_t || !x || !time || !mats || !vec || !workspace || !out || n < 0 || N < 1)
+    return SBI_AMD_E_BADARG;
+  rc = np_iid_envelope(pl, N);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  FmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.packed = packed; a.zstats = zstats; a.theta = theta_t; a.times = time; a.n = n; a.t_rows = 1; a.steps = 1;
+  a.v_out = out; a.ntiles = (int)((n + FM_ROWS - 1) / FM_ROWS);
+  NpIidArgs q;
+  memset(&q, 0, sizeof(q));
+  q.xs = x; q.N = (int)N; q.lam = lam; q.mats = mats; q.vecs = vec;
+  return np_iid_launch<false>(pl, a, q, workspace, (hipStream_t)stream);
+}
+
+int sbi_amd_npse_sample_sde_iid(const sbi_amd_npse_config* cfg, const float* packed, const float* zstats,
+                                const float* base, const float* x, int64_t N, const float* ts, int32_t steps, float eta,
+                                const float* lam, const float* step_mats, const float* step_vecs, const float* noise,
+                                uint64_t seed, int64_t row_offset, int64_t n, float* workspace, float* theta_out,
+                                void* stream) {
+  FmPlan pl;
+  int rc = np_build_plan(cfg, &pl);
+  if (rc) return rc;
+  if (!packed || !zstats || !base || !x || !ts || !workspace || !theta_out || n < 0 || N < 1 || steps < 0 ||
+      row_offset < 0 || !(eta > 0.f) || (steps > 0 && (!step_mats || !step_vecs)))
+    return SBI_AMD_E_BADARG;
+  if (steps > 65535) return SBI_AMD_E_UNSUPPORTED;
+  rc = np_iid_envelope(pl, N);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  FmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.packed = packed; a.zstats = zstats; a.times = ts; a.n = n; a.t_rows = 1;
+  a.steps = steps; a.eta = eta; a.base = base; a.sde_noise = noise; a.seed = seed; a.row_offset = row_offset;
+  a.v_out = theta_out; a.ntiles = (int)((n + FM_ROWS - 1) / FM_ROWS);
+  NpIidArgs q;
+  memset(&q, 0, sizeof(q));
+  q.xs = x; q.N = (int)N; q.lam = lam; q.mats = step_mats; q.vecs = step_vecs;
+  return np_iid_launch<true>(pl, a, q, workspace, (hipStream_t)stream);
+}
+
+int sbi_amd_npse_compose_iid(const float* s, const float* theta, const float* lam, const float* mats, const float* vec,
+                             int64_t n, int64_t N, int32_t D, float* out, void* stream) {
+  if (!s || !theta || !mats || !vec || !out || n < 0 || N < 1 || N > 0x7fffffff / 128 || D < 1 || D > 128)
+    return SBI_AMD_E_BADARG;
+  if (n == 0) return 0;
+  if (n > 0x7fffffff) return SBI_AMD_E_UNSUPPORTED;
+  hipLaunchKernelGGL(np_compose_kernel, dim3((unsigned)n), dim3(128), 0, (hipStream_t)stream, s, theta, lam, mats, vec,
+                     (int)N, (int)D, out);
+  return (int)hipGetLastError();
+}
+
+int sbi_amd_npse_sde_normals(uint64_t seed, int64_t row_offset, int32_t k, int64_t n, int32_t D, float* out,
+                              void* stream) {
+  if (!out || n < 0 || row_offset < 0 || k < 0 || D < 1 || D > 128) return SBI_AMD_E_BADARG;
+  if (n == 0) return 0;
+  FmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = n; a.seed = seed; a.row_offset = row_offset;
+  const long long threads = n * ((D + 3) / 4);
+  hipLaunchKernelGGL(np_normals_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a,
+                     (int)D, (int)k, out);
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -11,10 +11,19 @@ integrate d theta / dt = v(theta, t; x_o) from t_max to t_min, reject draws outs
 draw theta ~ N(mean_base, std_base) at ``ts[0]`` and take ``len(ts) - 1`` Euler-Maruyama steps of the reverse SDE, all in
 one launch per batch (``sbi_amd_npse_sample_sde``).  The draws come from Philox keyed by a seed taken from torch's
 generator once per call and indexed by the candidate's running number, so for a given ``torch.manual_seed`` the returned
-samples do NOT depend on how ``max_sampling_batch_size`` splits the work.  Refused with ``NotImplementedError``:
-correctors, predictors other than "euler_maruyama", iid observations (several rows of ``x`` outside
-``sample_batched``: sbi's fnpe / gauss / auto_gauss / jac_gauss score composition) and ``log_prob`` of a score-based
-posterior (it needs the divergence of ``ode_fn``).
+samples do NOT depend on how ``max_sampling_batch_size`` splits the work.
+
+Several rows of ``x`` in ``sample`` are N iid observations (:331-397 with ``iid_method``, default "auto_gauss"): the score
+of every step is the fnpe / gauss / auto_gauss composition of the per-observation scores
+(``sbi_amd.inference.potentials.vector_field_adaptor``: its theta-independent part is tabulated in fp64 on the host once
+per call).  Two legs evaluate it with the same Philox keying: a host loop with one ``sbi_amd_npse_score`` launch per step
+on the n N expanded rows and a per-row composition kernel (the default: it measured faster, profiles/npse_iid_bench.json), and
+the fused sampler ``sbi_amd_npse_sample_sde_iid`` (all steps in one launch; D <= 16, N <= 1024, at most 65535 steps).  The composition runs on a ROCm device only: a posterior on any other
+device refuses iid observations and ``iid_method``.
+
+Refused with ``NotImplementedError``: correctors, guidance, predictors other than "euler_maruyama", ``iid_method``
+"jac_gauss", gauss / auto_gauss under a non-Gaussian prior, iid observations with ``sample_with="ode"`` or with a
+flow-matching estimator, and ``log_prob`` of a score-based posterior (it needs the divergence of ``ode_fn``).
 """
 
 from __future__ import annotations
@@ -55,9 +64,16 @@ class VectorFieldPosterior:
         if x.dim() == len(cshape):
             x = x.unsqueeze(0)
         if self._is_score() and x.dim() == len(cshape) + 1 and x.shape[0] > 1 and x.shape[1:] == cshape:
-            raise NotImplementedError("sbi_amd NPSE: iid observations (several rows of x: sbi's fnpe / gauss / auto_gauss"
-                                      " / jac_gauss score composition) are not implemented; one observation per call, "
-                                      "or sample_batched for independent observations")
+            if not self._on_rocm():
+                raise NotImplementedError("sbi_amd NPSE: iid observations (several rows of x: the fnpe / gauss / auto_gauss "
+                                          "score composition) run on the device only; this posterior lives on "
+                                          f"{self._device!r}.  One observation per call, or sample_batched for "
+                                          "independent observations")
+            return x.to(self._device).contiguous()
+        if not self._is_score() and x.dim() == len(cshape) + 1 and x.shape[0] > 1 and x.shape[1:] == cshape:
+            raise NotImplementedError("sbi_amd FMPE: sampling given iid observations (several rows of x) is not "
+                                      "implemented: the score composition runs for score estimators (NPSE) only; "
+                                      "log_prob accepts iid observations, sample_batched independent ones")
         if x.shape[0] != 1 or x.shape[1:] != cshape:
             raise ValueError(f"expected one observation of shape {tuple(cshape)}, got {tuple(x.shape)}; use "
                              "sample_batched for several observations")
@@ -70,6 +86,9 @@ class VectorFieldPosterior:
             raise ValueError("Context `x` needed when a default has not been set. Use `.set_default_x(x)` or pass "
                              "`x` explicitly.")
         return self._x
+
+    def _on_rocm(self) -> bool:
+        return torch.device(self._device).type == "cuda"
 
     def _is_score(self) -> bool:
         from sbi_amd.neural_nets.estimators.score_estimator import ConditionalScoreEstimator
@@ -85,7 +104,12 @@ class VectorFieldPosterior:
         if predictor != "euler_maruyama":
             raise NotImplementedError(f"sbi_amd NPSE implements the 'euler_maruyama' predictor only, got {predictor!r}")
         if iid_method is not None:
-            raise NotImplementedError("sbi_amd NPSE: iid score composition (iid_method) is not implemented")
+            from sbi_amd.inference.potentials.vector_field_adaptor import get_iid_method
+
+            get_iid_method(iid_method)        # unknown names and jac_gauss are refused here
+            if not self._on_rocm():
+                raise NotImplementedError("sbi_amd NPSE: iid score composition (iid_method) runs on the device only; this "
+                                          f"posterior lives on {self._device!r}")
         params = dict(predictor_params or {})
         eta = float(params.pop("eta", 1.0))
         if params:
@@ -109,6 +133,24 @@ class VectorFieldPosterior:
             return sample_sde_loop(est, num_samples, cond, ts, eta)
         return sample_sde_fused(est, num_samples, cond, ts, eta, None, seed, row_offset)
 
+    def _iid_setup(self, x: Tensor, grid: Tensor, iid_method: Optional[str], iid_params: Optional[dict]):
+        """Tables of the composed score at grid[:-1] on the device: (lam, step_mats, step_vecs, base_scale)."""
+        from sbi_amd.inference.potentials.vector_field_adaptor import get_iid_method
+
+        fn = get_iid_method(iid_method or "auto_gauss")(self.vector_field_estimator, self.prior, device=self._device,
+                                                        **(iid_params or {}))
+        tb = fn.tables(grid[:-1].cpu(), x)
+        return (*tb.on(self._device), tb.base_scale)
+
+    @torch.no_grad()
+    def sample_via_sde_iid(self, num_samples: int, x: Tensor, ts: Tensor, tables, eta: float = 1.0, seed: int = 0,
+                           row_offset: int = 0) -> Tensor:
+        from sbi_amd.neural_nets.estimators.score_estimator import sample_sde_iid
+
+        lam, mats, vecs, base_scale = tables
+        return sample_sde_iid(self.vector_field_estimator, num_samples, x, ts, lam, mats, vecs, eta, seed, row_offset,
+                              base_scale)
+
     @torch.no_grad()
     def sample_via_ode(self, num_samples: int, x: Tensor) -> Tensor:
         est = self.vector_field_estimator
@@ -123,21 +165,35 @@ class VectorFieldPosterior:
                sample_with: Optional[str] = None, show_progress_bars: bool = False,
                reject_outside_prior: bool = True, predictor: str = "euler_maruyama", corrector: Optional[str] = None,
                predictor_params: Optional[dict] = None, corrector_params: Optional[dict] = None, steps: int = 500,
-               ts: Optional[Tensor] = None, iid_method: Optional[str] = None, **unsupported) -> Tensor:
+               ts: Optional[Tensor] = None, iid_method: Optional[str] = None, iid_params: Optional[dict] = None,
+               guidance_method: Optional[str] = None, guidance_params: Optional[dict] = None, **unsupported) -> Tensor:
         sample_with = sample_with or self.sample_with
         if sample_with not in ("ode", "sde"):
             raise ValueError(f"Expected sample_with to be 'ode' or 'sde', but got {sample_with}.")
+        if guidance_method is not None or guidance_params:
+            raise NotImplementedError("sbi_amd NPSE: guidance is not implemented; what runs: the plain score and the "
+                                      "fnpe / gauss / auto_gauss composition of iid observations")
         if sample_with == "sde":
             grid, eta, seed = self._sde_setup(steps, ts, predictor, corrector, predictor_params, corrector_params,
                                               iid_method)
         x = self._x_else_default_x(x)
+        iid = None            # one observation: iid_method is accepted and ignored, as in sbi
+        if x.shape[0] > 1:
+            if sample_with != "sde":
+                raise NotImplementedError("sbi_amd NPSE: iid observations are sampled with sample_with='sde' only (the "
+                                          "composed score drives the reverse SDE)")
+            iid = self._iid_setup(x, grid, iid_method, iid_params)
         num = int(torch.Size(sample_shape).numel())
         cap = max_sampling_batch_size or self.max_sampling_batch_size
         out, have, tries, drawn = [], 0, 0, 0
         while have < num:
             n = min(cap, max(num - have, 16))
-            draws = self.sample_via_ode(n, x) if sample_with == "ode" else \
-                self.sample_via_sde(n, x, grid, eta, seed, row_offset=drawn)
+            if iid is not None:
+                draws = self.sample_via_sde_iid(n, x, grid, iid, eta, seed, row_offset=drawn)
+            elif sample_with == "ode":
+                draws = self.sample_via_ode(n, x)
+            else:
+                draws = self.sample_via_sde(n, x, grid, eta, seed, row_offset=drawn)
             drawn += n
             if reject_outside_prior and self.prior is not None:
                 draws = draws[within_support(self.prior, draws)]

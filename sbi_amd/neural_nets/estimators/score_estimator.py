@@ -147,6 +147,162 @@ def sample_sde_loop(est: "ConditionalScoreEstimator", n: int, x: Tensor, ts: Ten
     return theta
 
 
+# --------------------------------------------------------------------- iid observations (include/sbi_amd_npse_iid.h)
+IID_FUSED_MAX_D, IID_FUSED_MAX_N = 16, 1024
+# which leg `sample_sde_iid` / `score_iid` take inside the fused envelope: the fused sampler measured slower than the
+# host loop at both benchmark shapes (profiles/npse_iid_bench.json; README, "NPSE with iid observations")
+IID_DEFAULT_FUSED = False
+
+
+def iid_fused_supported(est: "ConditionalScoreEstimator", N: int, steps: int = 0) -> bool:
+    """The envelope of the fused kernels: D <= 16 (one MFMA tile per table), N <= 1024, steps <= 65535."""
+    return est.input_shape[0] <= IID_FUSED_MAX_D and 1 <= N <= IID_FUSED_MAX_N and steps <= 65535
+
+
+def _iid_workspace(est, N: int, dev) -> Tensor:
+    need = _lib.load().sbi_amd_npse_iid_workspace_floats(_cfg(est), N)
+    if need < 0:
+        _lib.check(int(need), "npse_iid_workspace_floats")
+    return torch.empty(int(need), dtype=torch.float32, device=dev)
+
+
+def compose_iid(s: Tensor, theta: Tensor, lam: Optional[Tensor], mats: Tensor, vec: Tensor) -> Tensor:
+    """Linv (C sum_i s_i + sum_i Lam_i s_i) + A theta + b: s (n, N, D), theta (n, D), lam (N, D, D) or None,
+    mats (3, D, D), vec (D,).  One block per row with sequential sums (``sbi_amd_npse_compose_iid``), not BLAS
+    products: rocBLAS picks its kernel by the batch shape, which would make a row's low bits depend on how the rows are
+    split into calls."""
+    s, theta, mats, vec = s.contiguous(), theta.contiguous(), mats.contiguous(), vec.contiguous()
+    lam = None if lam is None else lam.contiguous()
+    dev = _lib.require_device(s, theta, lam, mats, vec)
+    n, N, D = s.shape
+    out = torch.empty_like(theta)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _lib.load().sbi_amd_npse_compose_iid(_lib.ptr(s), _lib.ptr(theta), _lib.ptr(lam), _lib.ptr(mats),
+                                                  _lib.ptr(vec), n, N, D, _lib.ptr(out), _lib.current_stream(dev))
+    _lib.check(rc, "npse_compose_iid")
+    return out
+
+
+def score_iid_fused(est: "ConditionalScoreEstimator", theta_t: Tensor, xs: Tensor, time: Tensor, lam: Optional[Tensor],
+                    mats: Tensor, vec: Tensor) -> Tensor:
+    """Composed score of the N observations xs (N, C) at theta_t (n, D) and one time, in one launch."""
+    net = est.net
+    dev = _lib.require_device(theta_t, xs, time, net.flat_params, lam, mats, vec)
+    n, N = theta_t.shape[0], xs.shape[0]
+    out = torch.empty_like(theta_t)
+    if n == 0:
+        return out
+    ws = _iid_workspace(est, N, dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().sbi_amd_npse_score_iid(
+            _cfg(est), _lib.ptr(packed_weights(net)), _lib.ptr(net.zstats), _lib.ptr(theta_t), _lib.ptr(xs), N,
+            _lib.ptr(time), _lib.ptr(lam), _lib.ptr(mats), _lib.ptr(vec), n, _lib.ptr(ws), _lib.ptr(out),
+            _lib.current_stream(dev))
+    _lib.check(rc, "npse_score_iid")
+    return out
+
+
+@torch.no_grad()
+def score_iid_loop(est: "ConditionalScoreEstimator", theta_t: Tensor, xs: Tensor, time: Tensor, lam: Optional[Tensor],
+                   mats: Tensor, vec: Tensor) -> Tensor:
+    """The same score from one `sbi_amd_npse_score` launch on the n N expanded rows and the per-row composition kernel."""
+    n, N, D = theta_t.shape[0], xs.shape[0], theta_t.shape[1]
+    s = score_call(est, theta_t.repeat_interleave(N, dim=0).contiguous(), xs.repeat(n, 1).contiguous(),
+                   time.reshape(1).contiguous())
+    return compose_iid(s.reshape(n, N, D), theta_t, lam, mats, vec)
+
+
+def score_iid(est, theta_t, xs, time, lam, mats, vec) -> Tensor:
+    if IID_DEFAULT_FUSED and iid_fused_supported(est, xs.shape[0]):
+        return score_iid_fused(est, theta_t, xs, time, lam, mats, vec)
+    return score_iid_loop(est, theta_t, xs, time, lam, mats, vec)
+
+
+def _iid_base(est, base_scale: float) -> Tensor:
+    return torch.cat([est.mean_base.reshape(-1), est.std_base.reshape(-1) * base_scale]).to(torch.float32).contiguous()
+
+
+def sample_sde_iid_fused(est: "ConditionalScoreEstimator", n: int, xs: Tensor, ts: Tensor, lam: Optional[Tensor],
+                         step_mats: Tensor, step_vecs: Tensor, eta: float = 1.0, noise: Optional[Tensor] = None,
+                         seed: int = 0, row_offset: int = 0, base_scale: float = 1.0) -> Tensor:
+    """`sample_sde_fused` with the score of step k replaced by the composed score of the N observations xs (N, C):
+    step_mats (steps, 3, D, D) and step_vecs (steps, D) are the tables at ts[:-1].  Same Philox keying and `noise`
+    contract; ``base_scale`` multiplies std_base of the initial draw (fnpe: 1 / sqrt(N))."""
+    net = est.net
+    base = _iid_base(est, base_scale)
+    dev = _lib.require_device(xs, ts, net.flat_params, base, noise, lam, step_mats, step_vecs)
+    D, N = est.input_shape[0], xs.shape[0]
+    steps = ts.numel() - 1
+    if noise is not None and tuple(noise.shape) != (steps + 1, n, D):
+        raise ValueError(f"noise must have shape {(steps + 1, n, D)}, got {tuple(noise.shape)}")
+    if tuple(step_mats.shape) != (steps, 3, D, D) or tuple(step_vecs.shape) != (steps, D):
+        raise ValueError(f"tables must have shapes {(steps, 3, D, D)} and {(steps, D)}")
+    out = torch.empty(n, D, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    ws = _iid_workspace(est, N, dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().sbi_amd_npse_sample_sde_iid(
+            _cfg(est), _lib.ptr(packed_weights(net)), _lib.ptr(net.zstats), _lib.ptr(base), _lib.ptr(xs), N,
+            _lib.ptr(ts), steps, float(eta), _lib.ptr(lam), _lib.ptr(step_mats), _lib.ptr(step_vecs), _lib.ptr(noise),
+            int(seed) & (2**64 - 1), int(row_offset), n, _lib.ptr(ws), _lib.ptr(out), _lib.current_stream(dev))
+    _lib.check(rc, "npse_sample_sde_iid")
+    return out
+
+
+def sde_normals(n: int, D: int, k: int, seed: int, row_offset: int, device) -> Tensor:
+    """(n, D) standard-normal draws z_k of the SDE samplers for rows row_offset .. row_offset + n - 1 under ``seed``."""
+    out = torch.empty(n, D, dtype=torch.float32, device=device)
+    if n:
+        with torch.cuda.device(device):
+            rc = _lib.load().sbi_amd_npse_sde_normals(int(seed) & (2**64 - 1), int(row_offset), int(k), n, D,
+                                                      _lib.ptr(out), _lib.current_stream(out.device))
+        _lib.check(rc, "npse_sde_normals")
+    return out
+
+
+@torch.no_grad()
+def sample_sde_iid_loop(est: "ConditionalScoreEstimator", n: int, xs: Tensor, ts: Tensor, lam: Optional[Tensor],
+                        step_mats: Tensor, step_vecs: Tensor, eta: float = 1.0, noise: Optional[Tensor] = None,
+                        base_scale: float = 1.0, seed: Optional[int] = None, row_offset: int = 0) -> Tensor:
+    """The plain path: per step one score launch on the n N expanded rows, then composition and update in torch.  The
+    route outside the fused envelope and the baseline the fused sampler is measured against.  Draws: ``noise``, else
+    with a ``seed`` the fused sampler's own Philox draws (same keying, so the result does not depend on how rows are
+    split into calls -- bit for bit, since score, composition and update are all row-wise), else torch's generator."""
+    D, N = est.input_shape[0], xs.shape[0]
+    dev = xs.device
+
+    def draw(k):
+        if noise is not None:
+            return noise[k]
+        if seed is not None:
+            return sde_normals(n, D, k, seed, row_offset, dev)
+        return torch.randn(n, D, device=dev)
+
+    theta = (est.mean_base + est.std_base * base_scale * draw(0)).contiguous()
+    xe = xs.repeat(n, 1).contiguous()
+    for k in range(1, ts.numel()):
+        t1, t0 = ts[k - 1], ts[k]
+        dt = t1 - t0
+        g = est.diffusion_fn(theta, t1.reshape(1))
+        f = est.drift_fn(theta, t1.reshape(1))
+        s = score_call(est, theta.repeat_interleave(N, dim=0).contiguous(), xe, t1.reshape(1).contiguous())
+        sc = compose_iid(s.reshape(n, N, D), theta, lam, step_mats[k - 1], step_vecs[k - 1])
+        theta = (theta - (f - (1 + eta**2) / 2 * g**2 * sc) * dt + eta * g * draw(k) * torch.sqrt(dt)).contiguous()
+    return theta
+
+
+def sample_sde_iid(est, n, xs, ts, lam, step_mats, step_vecs, eta=1.0, seed=0, row_offset=0, base_scale=1.0,
+                   noise=None) -> Tensor:
+    """The default leg: the host loop unless ``IID_DEFAULT_FUSED`` selects the fused sampler inside its envelope.  Both
+    draw ``noise`` if given, else Philox keyed by (seed, row + row_offset, step, dim)."""
+    if IID_DEFAULT_FUSED and iid_fused_supported(est, xs.shape[0], ts.numel() - 1):
+        return sample_sde_iid_fused(est, n, xs, ts, lam, step_mats, step_vecs, eta, noise, seed, row_offset, base_scale)
+    return sample_sde_iid_loop(est, n, xs, ts, lam, step_mats, step_vecs, eta, noise, base_scale, seed, row_offset)
+
+
 class _DSMLossFn(torch.autograd.Function):
     """Autograd bridge: per-row loss whose backward hands sum_i g_i dloss_i/dparams to ``flat_params.grad``
     (the fused kernels run again with the incoming g as row weights)."""
