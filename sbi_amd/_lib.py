@@ -444,6 +444,23 @@ _SIGNATURES_ABC = {
          c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_mog.h (NPE-A: the analytic MoG proposal correction, log_prob / sample of an arbitrary mixture)
+_SIGNATURES_MOG = {
+    "sbi_amd_mog_correct_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32, c_int32, c_int64]),
+    "sbi_amd_mog_correct": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+         c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_mog_log_prob": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+         c_void_p, c_void_p]),
+    "sbi_amd_mog_sample": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 
 def exported_symbols():
     return list(_SIGNATURES)
@@ -471,6 +488,10 @@ def exported_symbols_mnle():
 
 def exported_symbols_mdn():
     return list(_SIGNATURES_MDN)
+
+
+def exported_symbols_mog():
+    return list(_SIGNATURES_MOG)
 
 
 def exported_symbols_lc2st():
@@ -531,7 +552,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     lib = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_NPSE_IID, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
-                                      **_SIGNATURES_MMD, **_SIGNATURES_ABC}.items():
+                                      **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

@@ -89,6 +89,15 @@ class DirectPosterior:
         self._leakage_density_correction_factor = None
         return self
 
+    # -- what is sampled and evaluated (NPE_A_Posterior puts the corrected mixture here) --
+    def _candidate_sampler(self):
+        """`f(sample_shape, condition=x) -> (*sample_shape, B, D)`: the draws that are then tested against the prior."""
+        return self.posterior_estimator.sample
+
+    def _estimator_log_prob(self, theta: Tensor, x: Tensor) -> Tensor:
+        """(S, B, D), (B, ...) -> (S, B): the density before the support mask and the leakage correction."""
+        return self.posterior_estimator.log_prob(theta, condition=x)
+
     # -- sampling -----------------------------------------------------------------------
     def _batch_cap(self, requested: Optional[int]) -> int:
         return self.max_sampling_batch_size if requested is None else requested
@@ -100,7 +109,7 @@ class DirectPosterior:
         (direct_posterior.py:177-213 -> rejection.py:230-457); without rejection the raw draws."""
         est = self.posterior_estimator
         if not reject_outside_prior:
-            return est.sample(torch.Size([how_many]), condition=x)
+            return self._candidate_sampler()(torch.Size([how_many]), condition=x)
         def inside_prior(candidates: Tensor) -> Tensor:
             return within_support(self.prior, candidates)
 
@@ -126,7 +135,7 @@ class DirectPosterior:
                                                    torch.full((d_ev,), float("inf"), device=x.device))
                     inside_prior.box_bounds = cached
         kept, _acceptance = rejection.accept_reject_sample(
-            est.sample, inside_prior, how_many,
+            self._candidate_sampler(), inside_prior, how_many,
             show_progress_bars=show_progress_bars, max_sampling_batch_size=batch_cap,
             proposal_sampling_kwargs=dict(condition=x), alternative_method="build_posterior(..., sample_with='mcmc')",
             max_sampling_time=max_sampling_time, return_partial_on_timeout=return_partial_on_timeout,
@@ -182,7 +191,7 @@ class DirectPosterior:
             raise ValueError(".log_prob() supports only `batchsize == 1`. Use `.log_prob_batched()` for many "
                              "observations.")
         with torch.set_grad_enabled(track_gradients):
-            unnorm = est.log_prob(theta_sbe, condition=x_be).squeeze(1)
+            unnorm = self._estimator_log_prob(theta_sbe, x_be).squeeze(1)
             in_support = within_support(self.prior, theta)
             masked = torch.where(in_support, unnorm,
                                  torch.tensor(float("-inf"), dtype=torch.float32, device=self._device))
@@ -201,7 +210,7 @@ class DirectPosterior:
             if theta.dim() == len(est.input_shape) + 2 else theta.unsqueeze(0)
         x = reshape_to_batch_event(self._x_else_default_x(x), event_shape=est.condition_shape)
         with torch.set_grad_enabled(track_gradients):
-            unnorm = est.log_prob(theta, condition=x)
+            unnorm = self._estimator_log_prob(theta, x)
             in_support = within_support(self.prior, theta)
             masked = torch.where(in_support, unnorm,
                                  torch.tensor(float("-inf"), dtype=torch.float32, device=self._device))
@@ -220,7 +229,7 @@ class DirectPosterior:
 
         def acceptance_at(x_: Tensor) -> Tensor:
             return rejection.accept_reject_sample(
-                proposal=self.posterior_estimator.sample,
+                proposal=self._candidate_sampler(),
                 accept_reject_fn=lambda theta: within_support(self.prior, theta),
                 num_samples=num_rejection_samples, show_progress_bars=show_progress_bars,
                 sample_for_correction_factor=True, max_sampling_batch_size=rejection_sampling_batch_size,

@@ -108,6 +108,8 @@ class ImproperEmpirical:
 
 
 class PosteriorEstimatorTrainer:
+    _warns_atomic_loss = True      # (NPE-A trains every round by maximum likelihood: the warning would be wrong)
+
     def __init__(self, prior: Optional[Distribution] = None,
                  density_estimator: Union[str, NSFConfig, Callable, None] = None, device: str = "cpu",
                  logging_level: Union[int, str] = "WARNING", summary_writer=None, tracker=None,
@@ -228,7 +230,7 @@ class PosteriorEstimatorTrainer:
             )
         is_neural = hasattr(proposal, "posterior_estimator") or hasattr(
             getattr(proposal, "potential_fn", None), "posterior_estimator")   # MCMC / rejection posteriors
-        if not is_neural:
+        if not is_neural and self._warns_atomic_loss:
             warnings.warn(
                 "The proposal you passed is neither the prior nor a neural posterior: the atomic multi-round loss "
                 "will be used. If the parameters were sampled from the prior, pass proposal=None.", stacklevel=3,
@@ -313,6 +315,11 @@ class PosteriorEstimatorTrainer:
         """Per-row losses of a batch without the atomic correction (validation, and training off the fused path)."""
         return net.loss(theta, x)
 
+    def _get_start_index(self, discard_prior_samples: bool) -> int:
+        """First round whose simulations train() uses (trainers/base.py `_get_start_index`): all of them, or all but
+        the prior's.  NPE-A overrides it: its per-row loss trains on the latest round only."""
+        return int(discard_prior_samples and self._round > 0)
+
     # ------------------------------------------------------------------ training
     def train(self, num_atoms: int = 10, training_batch_size: int = 200, learning_rate: float = 5e-4,
               validation_fraction: float = 0.1, stop_after_epochs: int = 20, max_num_epochs: int = 2**31 - 1,
@@ -340,7 +347,7 @@ class PosteriorEstimatorTrainer:
         atomic = self._round > 0 and not force_first_round_loss
         if atomic:
             print(f"Using {type(self).__name__} with atomic loss")
-        start_idx = int(discard_prior_samples and self._round > 0)
+        start_idx = self._get_start_index(discard_prior_samples)
         cfg = TrainConfig(training_batch_size=training_batch_size, learning_rate=learning_rate,
                           validation_fraction=validation_fraction, stop_after_epochs=stop_after_epochs,
                           max_num_epochs=max_num_epochs, clip_max_norm=clip_max_norm,
@@ -807,7 +814,8 @@ class NPE_C(PosteriorEstimatorTrainer):
     """NPE-C / APT (npe_c.py:91-440): maximum likelihood in the first round, the atomic proposal-posterior loss
     in later rounds (``append_simulations(theta, x, proposal=posterior)``).  The closed-form MoG correction
     (`_log_prob_proposal_posterior_mog`) applies to mixture-density estimators only and is not part of the
-    NSF path."""
+    NSF path: a mixture density network with a proposal is refused here -- use NPE_A for multi-round inference
+    on mixtures."""
 
 
 NPE = NPE_C   # sbi/inference/__init__.py:22

@@ -10,8 +10,11 @@ Parameters live in ONE flat fp32 ``nn.Parameter`` in torch order under the refer
 speaks those names (``net._hidden_net.0.weight`` ..., ``_transform_shift``, ``_transform_scale``,
 ``_embedding_net.0._mean`` / ``_std``) and ``load_state_dict()`` accepts them.
 
-Not implemented (refused by name): ``MoG.condition``, the closed-form MoG proposal correction of multi-round NPE-C /
-NPE-A, a custom ``hidden_net``, the MDN as a likelihood estimator, ``z_score_x="transform_to_unconstrained"``.
+Multi-round inference on this estimator is NPE-A (``sbi_amd.inference.NPE_A``: plain maximum likelihood every round,
+then the closed-form MoG correction of sbi_amd/neural_nets/estimators/mog_ops.py).
+
+Not implemented (refused by name): ``MoG.condition``, the closed-form MoG proposal correction inside NPE-C's loss
+(use NPE_A), a custom ``hidden_net``, the MDN as a likelihood estimator, ``z_score_x="transform_to_unconstrained"``.
 """
 
 from __future__ import annotations
@@ -19,7 +22,7 @@ from __future__ import annotations
 import math
 from collections import OrderedDict
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import ClassVar, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -250,13 +253,78 @@ class _MDNLogProbFn(torch.autograd.Function):
 
 @dataclass
 class MoG:
-    """Light container of a batch of mixtures (the reference's ``MoG`` fields): logits (B, K) unnormalised, means
-    (B, K, D), precision_factors (B, K, D, D) upper triangular, precisions = A^T A + epsilon I."""
+    """A batch of mixtures of Gaussians with sbi's ``MoG`` surface (neural_nets/estimators/mog.py): logits (B, K)
+    unnormalised, means (B, K, D), precisions (B, K, D, D), precision_factors (B, K, D, D) upper triangular with
+    precision = A^T A (derived by a Cholesky factorisation of precisions + 1e-6 I when not given).  ``log_prob`` and
+    ``sample`` run on the gfx950 kernels of include/sbi_amd_mog.h for float32 tensors on a ROCm device inside their
+    envelope, and as eager torch otherwise (sbi_amd/neural_nets/estimators/mog_ops.py).  NPE-A (``NPE_A``) corrects
+    these mixtures in closed form; ``condition`` is not implemented."""
 
     logits: Tensor
     means: Tensor
     precisions: Tensor
-    precision_factors: Tensor
+    precision_factors: Optional[Tensor] = None
+
+    _CHOLESKY_EPSILON: ClassVar[float] = 1e-6
+
+    def __post_init__(self) -> None:
+        if self.logits.dim() != 2:
+            raise ValueError(f"logits must be 2D (batch_size, num_components), got {self.logits.dim()}D")
+        if self.means.dim() != 3:
+            raise ValueError(f"means must be 3D (batch_size, num_components, dim), got {self.means.dim()}D")
+        if self.precisions.dim() != 4:
+            raise ValueError(
+                f"precisions must be 4D (batch_size, num_components, dim, dim), got {self.precisions.dim()}D")
+        batch_size, num_components = self.logits.shape
+        if self.means.shape[:2] != (batch_size, num_components):
+            raise ValueError(f"means shape {self.means.shape} incompatible with logits shape {self.logits.shape}")
+        if self.precisions.shape[:2] != (batch_size, num_components):
+            raise ValueError(
+                f"precisions shape {self.precisions.shape} incompatible with logits shape {self.logits.shape}")
+        dim = self.means.shape[2]
+        if self.precisions.shape[2:] != (dim, dim):
+            raise ValueError(
+                f"precisions must be square matrices of size ({dim}, {dim}), got {self.precisions.shape[2:]}")
+        # one read-back for the three finiteness checks; the names are looked up only when something is wrong
+        finite = torch.stack([torch.isfinite(t).all() for t in (self.logits, self.means, self.precisions)]).tolist()
+        for ok, name in zip(finite, ("logits", "means", "precisions")):
+            if not ok:
+                raise ValueError(f"{name} contains NaN or Inf values")
+        if self.precision_factors is None:
+            eye = torch.eye(dim, device=self.precisions.device, dtype=self.precisions.dtype)
+            L, info = torch.linalg.cholesky_ex(self.precisions + self._CHOLESKY_EPSILON * eye)
+            if bool((info > 0).any()):
+                raise ValueError(
+                    "Failed to compute Cholesky decomposition of precision matrix. This indicates the precision "
+                    "matrix is not positive definite. Check that your MoG parameters are valid. "
+                    f"Original error: leading minor of order {int(info.max())} is not positive definite")
+            self.precision_factors = L.transpose(-2, -1)
+        else:
+            if self.precision_factors.shape != self.precisions.shape:
+                raise ValueError(f"precision_factors shape {self.precision_factors.shape} must match precisions "
+                                 f"shape {self.precisions.shape}")
+            if not bool(torch.isfinite(self.precision_factors).all()):
+                raise ValueError("precision_factors contains NaN or Inf values")
+
+    @property
+    def num_components(self) -> int:
+        return self.logits.shape[1]
+
+    @property
+    def dim(self) -> int:
+        return self.means.shape[2]
+
+    @property
+    def batch_shape(self) -> torch.Size:
+        return torch.Size([self.logits.shape[0]])
+
+    @property
+    def device(self) -> torch.device:
+        return self.logits.device
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return self.logits.dtype
 
     @property
     def log_weights(self) -> Tensor:
@@ -265,6 +333,55 @@ class MoG:
     @property
     def weights(self) -> Tensor:
         return torch.softmax(self.logits, dim=-1)
+
+    def log_prob(self, inputs: Tensor) -> Tensor:
+        """(batch_size, dim) -> (batch_size,); (sample_size, batch_size, dim) -> (sample_size, batch_size).  Batch
+        column b is evaluated under mixture row b (a one-row mixture serves every column)."""
+        from sbi_amd.neural_nets.estimators import mog_ops
+
+        squeeze = inputs.dim() == 2
+        if squeeze:
+            inputs = inputs.unsqueeze(0)
+        S, B, D = inputs.shape
+        if B != self.logits.shape[0] and self.logits.shape[0] != 1:
+            raise ValueError(f"inputs have batch size {B}, the mixture has {self.logits.shape[0]} rows")
+        out = mog_ops.mog_log_prob(self.logits, self.means, self.precisions, self.precision_factors,
+                                   inputs.reshape(S * B, D)).reshape(S, B)
+        return out[0] if squeeze else out
+
+    def sample(self, sample_shape: torch.Size = torch.Size()) -> Tensor:
+        """(*sample_shape, batch_size, dim): one uniform (component, inverse CDF of the weights) and `dim` normals
+        per draw, rows sample-major."""
+        from sbi_amd.neural_nets.estimators import mog_ops
+
+        shape = torch.Size(sample_shape)
+        n = int(shape.numel()) if len(shape) else 1
+        B, D = self.logits.shape[0], self.dim
+        u = torch.rand(n * B, device=self.device, dtype=self.dtype)
+        zeta = torch.randn(n * B, D, device=self.device, dtype=self.dtype)
+        out = mog_ops.mog_sample(self.logits, self.means, self.precision_factors, zeta, u=u)
+        return out.reshape(*shape, B, D) if len(shape) else out.reshape(B, D)
+
+    def to(self, device) -> "MoG":
+        return MoG(self.logits.to(device), self.means.to(device), self.precisions.to(device),
+                   self.precision_factors.to(device))
+
+    def detach(self) -> "MoG":
+        return MoG(self.logits.detach(), self.means.detach(), self.precisions.detach(),
+                   self.precision_factors.detach())
+
+    @classmethod
+    def from_gaussian(cls, mean: Tensor, covariance: Tensor) -> "MoG":
+        """A one-component mixture from a Gaussian's mean (dim,) / (B, dim) and covariance (dim, dim) / (B, dim, dim)."""
+        if mean.dim() == 1:
+            mean = mean.unsqueeze(0)
+        if covariance.dim() == 2:
+            covariance = covariance.unsqueeze(0)
+        precision = torch.linalg.inv(covariance)
+        factor = torch.linalg.cholesky(precision).transpose(-2, -1)
+        logits = torch.zeros(mean.shape[0], 1, device=mean.device, dtype=mean.dtype)
+        return cls(logits=logits, means=mean.unsqueeze(1), precisions=precision.unsqueeze(1),
+                   precision_factors=factor.unsqueeze(1))
 
     def condition(self, *args, **kwargs):
         raise NotImplementedError("sbi_amd: MoG.condition (conditioning a mixture on a subset of its dimensions) is "
