@@ -30,6 +30,13 @@
 extern "C" {
 #endif
 
+/* Envelope.  The per-field limits below (D <= 16, C <= 32, H <= 64, K <= 16, T <= 16, NB <= 4) are each necessary,
+ * not jointly sufficient: one transform's packed weight image and at least one wave's scratch must also fit the
+ * 160 KiB of LDS of a workgroup, else every launching entry point returns SBI_AMD_E_LDS (before any launch).  The
+ * image is dominated by the D*(3K-1) rows of the final layer (about H floats each), then by the 2 + NB hidden
+ * layers.  sbi's defaults (H 50, K 10, NB 2) fit every D <= 16; with 16 bins at H 50, NB 2 the limit is D <= 12; the
+ * corner D 16, C 32, H 64, K 16, NB 4 needs about 290 KB and is refused (there D <= 5 fits).  Configurations close to
+ * the limit run with fewer waves per workgroup.  sbi_amd_maf_plan_waves answers for a given configuration on the host. */
 typedef struct sbi_amd_maf_config {
   int32_t D;          /* theta features (1..16)                  flow.py:281  x_numel        */
   int32_t C;          /* embedded condition features (1..32)     flow.py:286  y_numel        */
@@ -74,6 +81,12 @@ int sbi_amd_maf_log_prob(const sbi_amd_maf_config* cfg, const float* packed, con
 int sbi_amd_maf_sample(const sbi_amd_maf_config* cfg, const float* packed, const float* zstats, const float* noise,
                        const float* x, int64_t n, int64_t x_rows, float* theta_out, float* logabsdet_out,
                        void* stream);
+
+/* Waves per workgroup (16 rows per wave, 1..8) that sbi_amd_maf_log_prob, sbi_amd_maf_sample and
+ * sbi_amd_maf_loss_fwd_bwd launch with for n rows, or the SBI_AMD_E_* they return for this configuration.  Host only:
+ * no launch, no device access.  The width halves from 8 while n rows make fewer than 256 workgroups, then steps down
+ * one wave at a time until the weight image plus the per-wave scratch fit the LDS. */
+int32_t sbi_amd_maf_plan_waves(const sbi_amd_maf_config* cfg, int64_t n);
 
 /* Training pass: loss_out[n] = -log p_n (optional), grad_out (param_count) = d( sum_n w_n loss_n ) / d params with
  * w_n = row_weight[n] (or uniform_weight when row_weight is NULL), grad_theta_out (n, D) optional.

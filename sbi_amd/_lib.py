@@ -244,6 +244,7 @@ _SIGNATURES = {
         c_int,
         [POINTER(MAFConfigC), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p],
     ),
+    "sbi_amd_maf_plan_waves": (c_int32, [POINTER(MAFConfigC), c_int64]),
     "sbi_amd_maf_train_workspace_floats": (c_int64, [POINTER(MAFConfigC), c_int64]),
     "sbi_amd_maf_loss_fwd_bwd": (
         c_int,

@@ -207,6 +207,15 @@ extern "C" int sbi_amd_maf_pack(const sbi_amd_maf_config* cfg, const float* para
   return (int)hipGetLastError();
 }
 
+// host-only: the workgroup width the three launching entry points below plan for n rows (or their refusal)
+extern "C" int32_t sbi_amd_maf_plan_waves(const sbi_amd_maf_config* cfg, int64_t n) {
+  if (!cfg || n < 1) return SBI_AMD_E_BADARG;
+  MafPlan mp;
+  int nw = 0;
+  const int rc = maf_plan_for_rows(cfg, n, 8, &mp, &nw);
+  return rc ? rc : nw;
+}
+
 extern "C" int sbi_amd_maf_log_prob(const sbi_amd_maf_config* cfg, const float* packed, const float* zstats,
                                     const float* theta, const float* x, int64_t n, int64_t x_rows, float* logp_out,
                                     float* noise_out, void* stream) {

@@ -91,6 +91,42 @@ def test_throughput_workgroup_size_minimises_rounds_over_the_cus():
     assert lib.sbi_amd_nsf_plan_waves(NSFHyper(D=10, C=10, hidden_features=100).c_config(), 4096, 0) == _lib.E_LDS
 
 
+def test_maf_workgroup_width_and_lds_envelope_are_host_side_answers():
+    """csrc/maf.hip::maf_plan_for_rows through `sbi_amd_maf_plan_waves` (no device): eight waves, halved while the rows
+    make fewer than 256 workgroups (thresholds 8161 / 16321 / 32641 rows), then one wave less at a time until the
+    transform's weight image plus the waves' scratch fit 160 KiB; E_LDS when not even one wave does -- which is well
+    inside the per-field limits of include/sbi_amd_maf.h (tests/test_maf_envelope_gpu.py runs these launches)."""
+    lib = _lib.load()
+
+    def nw(variant, D, C, H, K, NB, n=32641):
+        return lib.sbi_amd_maf_plan_waves(_lib.MAFConfigC(D, C, H, K, 2, NB, 3.0, 1e-3, 1e-3, 1e-3, 0, variant), n)
+
+    for v in (0, 1):
+        assert [nw(v, 5, 3, 32, 8, 1, n) for n in (1, 8160, 8161, 16320, 16321, 32640, 32641, 10**6)] == \
+            [1, 1, 2, 2, 4, 4, 8, 8]
+        assert nw(v, 10, 10, 50, 10, 2) == 8                     # sbi's defaults keep the full width
+        assert nw(v, 16, 32, 64, 16, 4) == _lib.E_LDS            # the corner of the per-field limits
+        for n in (1, 333, 8161):
+            assert nw(v, 16, 32, 64, 16, 4, n) == _lib.E_LDS
+        # the boundary: theta-dim 5 at that corner, 12 at hidden 50 / 16 bins / 2 blocks, all 16 at the defaults
+        assert [nw(v, D, 32, 64, 16, 4) for D in (4, 5, 6)] == [2, 1, _lib.E_LDS]
+        assert [nw(v, D, 10, 50, 16, 2) for D in (11, 12, 13)] == [2, 1, _lib.E_LDS]
+        assert [nw(v, D, 10, 50, 10, 2) for D in (10, 12, 14, 16)] == [8, 6, 5, 3]
+        assert nw(v, 13, 10, 50, 16, 1) == 1 and nw(v, 14, 10, 50, 16, 1) == _lib.E_LDS
+        assert nw(v, 16, 4, 64, 8, 3) == _lib.E_LDS
+    # LDS-forced widths (variant 0 / 1): every width 1 .. 8 is reachable
+    assert [nw(0, *c) for c in ((16, 4, 64, 8, 2), (16, 32, 32, 16, 1), (14, 32, 32, 16, 2), (16, 32, 50, 8, 1),
+                                (4, 32, 50, 16, 4), (16, 32, 32, 8, 2))] == [1, 2, 3, 5, 6, 7]
+    assert [nw(1, *c) for c in ((16, 32, 64, 8, 2), (16, 4, 64, 8, 2), (14, 32, 32, 16, 1), (16, 32, 50, 8, 1),
+                                (4, 32, 50, 16, 4), (8, 32, 32, 16, 1))] == [1, 2, 3, 5, 6, 7]
+    # refusals that are not about LDS keep their own codes
+    assert nw(0, 0, 4, 64, 8, 2) == _lib.E_BADARG and nw(0, 5, 3, 32, 7, 1) == _lib.E_UNSUPPORTED
+    assert nw(0, 5, 3, 32, 8, 1, n=0) == _lib.E_BADARG and nw(2, 5, 3, 32, 8, 1) == _lib.E_UNSUPPORTED
+    assert lib.sbi_amd_maf_plan_waves(None, 100) == _lib.E_BADARG
+    with pytest.raises(RuntimeError, match="more than 160 KiB of LDS"):
+        _lib.check(nw(0, 16, 32, 64, 16, 4), "maf_plan_waves")
+
+
 def test_training_envelope_and_refusals_are_host_side_decisions():
     """`sbi_amd_nsf_train_workspace_floats` answers on the host (no device call) whether a shape trains: the
     wave-specialised backward kernel's shapes, the generic training pass beyond them (theta-dim > 15, 3-4 blocks,
