@@ -1013,6 +1013,14 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
     // the guard-free mat-vec helpers read 16 floats from a ZW-float row: make sure that never is
     // uninitialised LDS (NaN x 0 = NaN)
     for (int i = id.lane; i < tp.w_total; i += 64) sc[i] = 0.f;
+    // Bs row = [z_id ; context ; 1 ; 0 ...]: only columns [0, in0] (in0 of either mask parity) ever hold anything but
+    // zero, and nobody but this wave writes its 16 rows.  So the zero padding is written here, once per launch, and a
+    // tile rewrites only the 4-column groups that reach below `bs_live` (static default layout: 4 of 12 stores and 12 of
+    // 24 LDS reads per lane are left in the prologue, which is pure critical path: the grad waves wait at K0 meanwhile).
+    // This wave's later stores to these rows are ordered behind the fill (one wave's LDS operations execute in order);
+    // the first S0 barrier publishes it to the grad waves.
+    const int bs_live = (pl.shape[0].in0 > pl.shape[1].in0 ? pl.shape[0].in0 : pl.shape[1].in0) + 1;
+    for (int i = id.lane; i < 16 * SS; i += 64) Bs[arow0 * SS + i] = 0.f;
     const LaneId id0 = id;
     // state, context, upstream gradient and row weight of the NEXT tile are requested a whole block phase
     // ahead (clamped addresses instead of predicated loads), so the tile prologue never waits on HBM
@@ -1082,11 +1090,12 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
           }
         }
         wave_lds_fence();
-          // conditioner-input row [z_id ; standardized context ; 1 ; 0 ...] -> static tile Bs (branch-free:
+        // conditioner-input row [z_id ; standardized context ; 1 ; 0 ...] -> static tile Bs (branch-free:
         // clamped reads + selects).  The context is x * (1/std): within 1 ulp of the forward kernel's
         // (x - mean) / std; it only feeds the B operand of d W0 / d Wc.
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
+          if (4 * u >= bs_live) break;     // zero since the launch began (wave-uniform; compile time in the static layout)
           const int k = id.g + 4 * u;
           const int c = k - S.d_id;
           const int cc = (c >= 0 && c < C) ? c : 0;
@@ -1098,7 +1107,6 @@ nsf_bwd_layer_kernel(const NsfPlan pl_, const TrainPlan tp_, const BwdIo io) {
           v = (k < S.d_id) ? zid : v;
           if (k < SS) Bs[trow * SS + k] = v;
         }
-        for (int k = 32 + id.g; k < SS; k += 4) Bs[trow * SS + k] = 0.f;
       }
       // ---- LULinear backward wrt its input (needs no forward values): g_u = L^T g_z, g_y = U^T g_u
       float gus_r[4] = {0.f, 0.f, 0.f, 0.f};     // g_u of dims 4 g + ii, kept for the LU parameter gradients
