@@ -105,6 +105,18 @@ class LC2STConfigC(Structure):
     ]
 
 
+class FCEmbedConfigC(Structure):
+    """Mirror of ``struct sbi_amd_fc_embed_config`` (include/sbi_amd_embed.h)."""
+
+    _fields_ = [("in_dim", c_int32), ("hidden", c_int32), ("out_dim", c_int32), ("num_layers", c_int32)]
+
+
+class PermInvConfigC(Structure):
+    """Mirror of ``struct sbi_amd_perminv_config`` (include/sbi_amd_embed.h)."""
+
+    _fields_ = [("trial", FCEmbedConfigC), ("head", FCEmbedConfigC), ("aggregation", c_int32)]
+
+
 _SIGNATURES = {
     "sbi_amd_nsf_param_count": (c_int64, [POINTER(NSFConfigC)]),
     "sbi_amd_nsf_layer_offset": (c_int64, [POINTER(NSFConfigC), c_int32]),
@@ -462,9 +474,30 @@ _SIGNATURES_MOG = {
          c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_embed.h (the embedding nets: FCEmbedding, PermutationInvariantEmbedding)
+_FCEP, _PIP = POINTER(FCEmbedConfigC), POINTER(PermInvConfigC)
+_SIGNATURES_EMBED = {
+    "sbi_amd_embed_param_count": (c_int64, [_FCEP, POINTER(c_int64)]),
+    "sbi_amd_embed_workspace_bytes": (c_int64, [_FCEP, c_int64]),
+    "sbi_amd_embed_plan": (c_int, [_FCEP, c_int64, c_int64, POINTER(c_int32), POINTER(c_int32)]),
+    "sbi_amd_fc_embed_forward": (c_int, [_FCEP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sbi_amd_fc_embed_backward": (
+        c_int, [_FCEP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_perminv_forward": (
+        c_int, [_PIP, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_perminv_backward": (
+        c_int,
+        [_PIP, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p]),
+}
+
 
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+def exported_symbols_embed():
+    return list(_SIGNATURES_EMBED)
 
 
 def exported_symbols_mmd():
@@ -553,7 +586,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     lib = ctypes.CDLL(str(path))
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_NPSE_IID, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
-                                      **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG}.items():
+                                      **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG,
+                                      **_SIGNATURES_EMBED}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

@@ -28,12 +28,14 @@ class DirectPosterior:
     def __init__(self, posterior_estimator: ConditionalDensityEstimator, prior: Distribution,
                  max_sampling_batch_size: int = 10_000, device: Optional[Union[str, torch.device]] = None,
                  x_shape: Optional[torch.Size] = None, enable_transform: bool = True,
-                 check_finite_x: bool = True):
+                 check_finite_x: bool = True, allow_nan_x: bool = False):
         self.posterior_estimator = posterior_estimator
         self.prior = prior
         self.max_sampling_batch_size = max_sampling_batch_size
         self.enable_transform = enable_transform
         self._check_finite_x = check_finite_x
+        # missing iid trials of x_o are NaN by design behind a PermutationInvariantEmbedding (Inf is still refused)
+        self._allow_nan_x = allow_nan_x
         if device is None:
             device = str(next(posterior_estimator.parameters()).device)
         self._device = process_device(device)
@@ -47,13 +49,20 @@ class DirectPosterior:
         self._purpose = "It samples the posterior network and rejects samples that lie outside of the prior bounds."
 
     # -- x handling ---------------------------------------------------------------------
+    _allow_nan_x = False      # (subclasses and copies made before the argument existed)
+
+    def _x_is_acceptable(self, x: Tensor) -> bool:
+        if self._allow_nan_x:
+            return not torch.isinf(x).any()
+        return bool(torch.isfinite(x).all())
+
     @property
     def default_x(self) -> Optional[Tensor]:
         return self._x
 
     def set_default_x(self, x: Tensor) -> "DirectPosterior":
         x = torch.as_tensor(x, dtype=torch.float32)
-        if self._check_finite_x and not torch.isfinite(x).all():
+        if self._check_finite_x and not self._x_is_acceptable(x):
             raise ValueError("x_o contains NaN or Inf values.")
         x = reshape_to_batch_event(x, self.posterior_estimator.condition_shape) if x.dim() <= len(
             self.posterior_estimator.condition_shape) + 1 else x
@@ -67,7 +76,7 @@ class DirectPosterior:
             # object at the same version was checked before and has not been written since
             seen = self.__dict__.get("_finite_x_seen")
             if self._check_finite_x and not (seen is not None and seen[0] is x and seen[1] == x._version):
-                if not torch.isfinite(x).all():
+                if not self._x_is_acceptable(x):
                     raise ValueError("x_o contains NaN or Inf values.")
                 self._finite_x_seen = (x, x._version)
             return x.to(self._device)

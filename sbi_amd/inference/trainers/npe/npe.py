@@ -752,6 +752,7 @@ class PosteriorEstimatorTrainer:
                         prior: Optional[Distribution] = None, sample_with: str = "direct",
                         direct_sampling_parameters: Optional[Dict[str, Any]] = None, **kwargs):
         from sbi_amd.inference.posteriors.direct_posterior import DirectPosterior
+        from sbi_amd.neural_nets.embedding_nets.permutation_invariant import masks_nan_trials
 
         if sample_with not in ("direct", "mcmc", "rejection"):
             raise NotImplementedError(
@@ -805,8 +806,10 @@ class PosteriorEstimatorTrainer:
                                                  theta_transform=mcmc_transform(prior, device=device), device=device,
                                                  **params)
             return deepcopy(self._posterior)
+        # a NaN-padded x_o (missing iid trials) is meaningful to a PermutationInvariantEmbedding only
         self._posterior = DirectPosterior(posterior_estimator=estimator, prior=prior, device=device,
-                                          **(direct_sampling_parameters or {}))
+                                          **{"allow_nan_x": masks_nan_trials(estimator),
+                                             **(direct_sampling_parameters or {})})
         return deepcopy(self._posterior)
 
 
