@@ -21,65 +21,21 @@ from sbi_amd import _lib
 from sbi_amd.neural_nets.estimators.mixed_density_estimator import (mnle_log_prob_call, mnle_loss_fwd_bwd,
                                                                     mnle_packed_weights, mnle_sample_call,
                                                                     mnle_trials_call, split_input)
-from sbi_amd.neural_nets.net_builders.mixed_nets import build_mnle
-from tests.mnle_oracle import MixedOracle, toy_log_likelihood, toy_sets, toy_simulator
+from tests.mnle_envelope import BASE_CONFIGS as CONFIGS
+from tests.mnle_envelope import category_values, mnle_pair_cpu, smooth_rows
+from tests.mnle_oracle import toy_log_likelihood, toy_sets, toy_simulator
 
 pytestmark = pytest.mark.gpu
 
-# name: (categories, C, discrete width, discrete blocks, embedding, hidden, K, T, context layers)
-CONFIGS = {
-    "defaults": ([2], 4, 50, 2, 50, 50, 10, 5, 1),
-    "multi": ([2, 5, 3], 3, 32, 1, 32, 32, 8, 2, 0),
-    "corner": ([16, 2, 7, 16], 64, 64, 4, 64, 64, 16, 8, 2),
-    "tiny": ([3], 1, 8, 1, 8, 8, 4, 1, 1),
-}
 ROWS = [1, 17, 333]
 E2E = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mnle_e2e.json")
-
-
-def category_values(cats):
-    """Raw values that are not the indices: {-1, 1}, {0, 2, 5, ...}, ..."""
-    out = []
-    for v, c in enumerate(cats):
-        if c == 2:
-            out.append(torch.tensor([-1.0, 1.0]))
-        else:
-            out.append(torch.cumsum(torch.arange(c, dtype=torch.float32) % 3 + 2, 0) - 2 + v)
-    return out
-
-
-def toy_data(cats, C, n, log_x, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    theta = torch.randn(n, C, generator=g) * 1.3 + 0.2
-    vals = category_values(cats)
-    idx = torch.stack([torch.randint(0, c, (n,), generator=g) for c in cats], 1)
-    idx[: max(cats)] = torch.stack([torch.arange(max(cats)) % c for c in cats], 1)      # every category is present
-    d = torch.stack([vals[v][idx[:, v]] for v in range(len(cats))], 1)
-    base = 0.5 * theta[:, 0] + 0.2 * idx[:, 0].float() + 0.4 * torch.randn(n, generator=g)
-    xc = torch.exp(0.5 * base) if log_x else base
-    return theta, torch.cat([xc[:, None], d], 1)
 
 
 @functools.lru_cache(maxsize=None)
 def mnle_pair(name, log_x=False, perturb=0.05, seed=1):
     """(fp32 restatement, fp64 restatement, HIP estimator, theta, x): identical perturbed weights and z-scoring."""
-    cats, C, Hd, NB, E, Hc, K, T, L = CONFIGS[name]
-    theta, x = toy_data(cats, C, 1000, log_x)
-    torch.manual_seed(seed)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        est = build_mnle(x, theta, log_transform_x=log_x, hidden_features=Hc, discrete_hidden_features=Hd,
-                         discrete_hidden_layers=NB, combined_embedding_features=E, num_bins=K, num_transforms=T,
-                         hidden_layers_spline_context=L, num_categories_per_variable=torch.tensor(cats))
-    oracle = MixedOracle(cats, category_values(cats), C, Hd, NB, E, Hc, K, T, L, 10.0, log_x)
-    oracle.set_zstats(est.net.zstats)
-    g = torch.Generator().manual_seed(seed + 100)
-    with torch.no_grad():
-        for p in oracle.parameters():
-            p.add_(perturb * torch.randn(p.shape, generator=g))
-    est.load_state_dict(oracle.state_dict())
-    assert torch.equal(est.net.flat_params.detach(), oracle.flat_params())
-    return oracle, copy.deepcopy(oracle).double(), est.cuda(), theta, x
+    oracle, oracle64, est, theta, x = mnle_pair_cpu(name, log_x, perturb, seed)
+    return oracle, oracle64, est.cuda(), theta, x
 
 
 def _errs(got, ref32, ref64):
@@ -193,31 +149,6 @@ def test_sample_follows_the_inverse_cdf_and_the_inverse_flow(name, log_x):
     full = est.sample_given(u.cuda(), noise.cuda(), theta_d.cuda()).cpu()
     assert torch.equal(full[keep][:, 1:].double(), x64[keep][:, 1:])            # raw values, not indices
     assert est.sample(torch.Size([3]), theta_d[:5].cuda()).shape == (3, 5, 1 + V)
-
-
-@functools.lru_cache(maxsize=None)
-def smooth_rows(name):
-    """Rows of the 1000-row pool on which the fp32 and the fp64 restatement take the same branch of every ReLU.
-
-    The networks are piecewise linear in their activations: a pre-activation within fp32 rounding of zero is positive
-    in one precision and negative in the other, and the fp64 gradient is then the derivative of a DIFFERENT piece than
-    the one any fp32 evaluation is on (the corner configuration has 2 240 ReLU inputs per row: at 1e-6 absolute
-    rounding error that is about one such row in 500).  Such a row shows in the references alone, as a jump in its
-    d loss / d theta between the two restatements (fp32 rounding moves that gradient by ~1e-5 of its size, a flipped
-    unit by far more); these rows are left out, their number is capped by the caller, and the kernels' output plays
-    no part in the choice."""
-    o32, o64, _, theta, x = mnle_pair(name, True)
-
-    def row_grads(o, dt):
-        th = theta.to(dt).clone().requires_grad_(True)
-        o.loss(x.to(dt), th).sum().backward()
-        o.zero_grad()
-        return th.grad.double()
-
-    g32, g64 = row_grads(o32, torch.float32), row_grads(o64, torch.float64)
-    rel = (g32 - g64).abs().max(1).values / g64.abs().max(1).values
-    keep = rel <= 1e-3
-    return torch.nonzero(keep)[:, 0], int((~keep).sum())
 
 
 @pytest.mark.parametrize("n", ROWS)
