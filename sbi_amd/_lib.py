@@ -491,9 +491,24 @@ _SIGNATURES_EMBED = {
          c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_cond.h (conditional-density grids: fill, fp64 moments / correlation coefficient, conditioned expand)
+_SIGNATURES_COND = {
+    "sbi_amd_cond_grid_fill": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_void_p, c_void_p]),
+    "sbi_amd_cond_grid_moments": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+         c_void_p]),
+    "sbi_amd_cond_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+}
+
 
 def exported_symbols():
     return list(_SIGNATURES)
+
+
+def exported_symbols_cond():
+    return list(_SIGNATURES_COND)
 
 
 def exported_symbols_embed():
@@ -587,7 +602,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_NPSE_IID, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
                                       **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG,
-                                      **_SIGNATURES_EMBED}.items():
+                                      **_SIGNATURES_EMBED, **_SIGNATURES_COND}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes
