@@ -80,16 +80,18 @@ __device__ __forceinline__ void mdn_gemm_T_reg(const float* __restrict__ w, cons
     for (int mt = 0; mt < 4; ++mt) acc[mt] = MFMA16(a0[4 * s * MDN_LDH + 16 * mt], bv, acc[mt]);
   }
 }
-// one 16-row tile of a component slice: rows 16 mt + 4 g + r of lane (j, g) (natural order), B = h2 fragments
+// one 16-row tile of a component slice: rows 16 mt + 4 g + r of lane (j, g) (natural order), B = h2 fragments.
+// The bias is added LAST: a chain that starts from it rounds every K-step at the bias's magnitude, and the raw
+// diagonal's bias can dwarf W h (raw entries near softplus's threshold of 20: 7 ulp of 20 against half an ulp).
 template <int KSH>
 __device__ __forceinline__ f4 mdn_head_tile(const float* __restrict__ wk, const float* __restrict__ bk,
                                             const LaneId& id, const f4 (&h)[4], int mt) {
-  f4 acc;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = bk[16 * mt + 4 * id.g + r];
+  f4 acc = {0.f, 0.f, 0.f, 0.f};
   const float* a0 = wk + (16 * mt + id.j) * MDN_LDH + id.g;
 #pragma unroll
   for (int s = 0; s < KSH; ++s) acc = MFMA16(a0[4 * s], h[s >> 2][s & 3], acc);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] += bk[16 * mt + 4 * id.g + r];
   return acc;
 }
 // all tiles of a slice -> the wave's row buffer sc[j][0 .. RP)

@@ -17,8 +17,9 @@ from sbi_amd import _lib
 from sbi_amd.neural_nets.estimators.mdn import (mdn_components_call, mdn_log_prob_call, mdn_loss_fwd_bwd,
                                                 mdn_packed_weights, mdn_sample_call)
 from sbi_amd.neural_nets.net_builders.mdn import build_mdn
-from tests.helpers import linear_gaussian_data
-from tests.mdn_oracle import MDNOracle
+from tests.mdn_envelope import errs as _errs
+from tests.mdn_envelope import mdn_pair_gpu
+from tests.mdn_envelope import packed_factors as _packed_factors
 from tests.parity_log import record
 
 pytestmark = pytest.mark.gpu
@@ -33,30 +34,10 @@ def _id(c):
     return "D%d-C%d-H%d-K%d" % c
 
 
-@functools.lru_cache(maxsize=None)
-def mdn_pair(D, C, H, K, perturb=0.05, seed=1):
-    """(fp32 restatement, fp64 restatement, HIP estimator, theta, x): identical perturbed weights and z-scoring."""
-    theta, x = linear_gaussian_data(1000, D, C)
-    torch.manual_seed(seed)
-    est = build_mdn(theta, x, hidden_features=H, num_components=K)
-    oracle = MDNOracle(D, C, H, K)
-    oracle.set_zstats(est.net.zstats)
-    g = torch.Generator().manual_seed(seed + 100)
-    with torch.no_grad():
-        for p in oracle.parameters():
-            p.add_(perturb * torch.randn(p.shape, generator=g))
-    est.load_state_dict(oracle.state_dict())
-    return oracle, copy.deepcopy(oracle).double(), est.cuda(), theta, x
-
-
-def _errs(got, ref32, ref64):
-    return (got.double().cpu() - ref64).abs().max().item(), (ref32.double() - ref64).abs().max().item()
-
-
-def _packed_factors(A, D):
-    idx = torch.arange(D)
-    r, c = torch.triu_indices(D, D, 1)
-    return torch.cat([A[..., idx, idx], A[..., r, c]], -1)
+def mdn_pair(D, C, H, K):
+    """(fp32 restatement, fp64 restatement, HIP estimator, theta, x): identical perturbed weights and z-scoring
+    (built once in tests/mdn_envelope.py and shared with the envelope tests)."""
+    return mdn_pair_gpu(D, C, H, K)
 
 
 @pytest.mark.parametrize("one_x", [False, True], ids=["paired", "one_x"])
