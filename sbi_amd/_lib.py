@@ -117,6 +117,13 @@ class PermInvConfigC(Structure):
     _fields_ = [("trial", FCEmbedConfigC), ("head", FCEmbedConfigC), ("aggregation", c_int32)]
 
 
+class CNNConfigC(Structure):
+    """Mirror of ``struct sbi_amd_cnn_config`` (include/sbi_amd_cnn.h)."""
+
+    _fields_ = [("ndim", c_int32), ("in_channels", c_int32), ("spatial", c_int32 * 2), ("num_conv_layers", c_int32),
+                ("out_channels", c_int32 * 4), ("kernel_size", c_int32), ("pool_kernel_size", c_int32)]
+
+
 _SIGNATURES = {
     "sbi_amd_nsf_param_count": (c_int64, [POINTER(NSFConfigC)]),
     "sbi_amd_nsf_layer_offset": (c_int64, [POINTER(NSFConfigC), c_int32]),
@@ -491,6 +498,17 @@ _SIGNATURES_EMBED = {
          c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_cnn.h (the convolution stack of CNNEmbedding)
+_CNNP = POINTER(CNNConfigC)
+_SIGNATURES_CNN = {
+    "sbi_amd_cnn_param_count": (c_int64, [_CNNP, POINTER(c_int64)]),
+    "sbi_amd_cnn_feature_count": (c_int64, [_CNNP]),
+    "sbi_amd_cnn_plan": (c_int, [_CNNP, c_int64, POINTER(c_int32), POINTER(c_int32)]),
+    "sbi_amd_cnn_workspace_bytes": (c_int64, [_CNNP, c_int64]),
+    "sbi_amd_cnn_forward": (c_int, [_CNNP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sbi_amd_cnn_backward": (c_int, [_CNNP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 # include/sbi_amd_cond.h (conditional-density grids: fill, fp64 moments / correlation coefficient, conditioned expand)
 _SIGNATURES_COND = {
     "sbi_amd_cond_grid_fill": (
@@ -513,6 +531,10 @@ def exported_symbols_cond():
 
 def exported_symbols_embed():
     return list(_SIGNATURES_EMBED)
+
+
+def exported_symbols_cnn():
+    return list(_SIGNATURES_CNN)
 
 
 def exported_symbols_mmd():
@@ -602,7 +624,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_NPSE_IID, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
                                       **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG,
-                                      **_SIGNATURES_EMBED, **_SIGNATURES_COND}.items():
+                                      **_SIGNATURES_EMBED, **_SIGNATURES_COND, **_SIGNATURES_CNN}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

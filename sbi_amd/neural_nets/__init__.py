@@ -5,4 +5,10 @@ from sbi_amd.neural_nets.net_builders.estimator_configs import (MAFConfig, MAFRQ
                                                                 NSFConfig,
                                                                 ResNetClassifierConfig, ZukoNSFConfig)
 from sbi_amd.neural_nets.net_builders.flow import build_maf  # noqa: F401,E402
-from sbi_amd.neural_nets.embedding_nets import FCEmbedding, PermutationInvariantEmbedding  # noqa: F401,E402
+from sbi_amd.neural_nets.embedding_nets import (  # noqa: F401,E402
+    CNNEmbedding,
+    FCEmbedding,
+    PermutationInvariantEmbedding,
+    calculate_filter_output_size,
+    get_new_cnn_output_size,
+)

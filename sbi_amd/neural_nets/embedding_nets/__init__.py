@@ -1,2 +1,7 @@
 from sbi_amd.neural_nets.embedding_nets.fully_connected import FCEmbedding  # noqa: F401
 from sbi_amd.neural_nets.embedding_nets.permutation_invariant import PermutationInvariantEmbedding  # noqa: F401
+from sbi_amd.neural_nets.embedding_nets.cnn import (  # noqa: F401
+    CNNEmbedding,
+    calculate_filter_output_size,
+    get_new_cnn_output_size,
+)
