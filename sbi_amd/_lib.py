@@ -124,6 +124,13 @@ class CNNConfigC(Structure):
                 ("out_channels", c_int32 * 4), ("kernel_size", c_int32), ("pool_kernel_size", c_int32)]
 
 
+class LRUConfigC(Structure):
+    """Mirror of ``struct sbi_amd_lru_config`` (include/sbi_amd_lru.h)."""
+
+    _fields_ = [("input_dim", c_int32), ("hidden_dim", c_int32), ("state_dim", c_int32), ("num_blocks", c_int32),
+                ("bidirectional", c_int32), ("aggregation", c_int32)]
+
+
 _SIGNATURES = {
     "sbi_amd_nsf_param_count": (c_int64, [POINTER(NSFConfigC)]),
     "sbi_amd_nsf_layer_offset": (c_int64, [POINTER(NSFConfigC), c_int32]),
@@ -509,6 +516,17 @@ _SIGNATURES_CNN = {
     "sbi_amd_cnn_backward": (c_int, [_CNNP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_lru.h (the recurrent stack of LRUEmbedding)
+_LRUP = POINTER(LRUConfigC)
+_SIGNATURES_LRU = {
+    "sbi_amd_lru_param_count": (c_int64, [_LRUP, POINTER(c_int64)]),
+    "sbi_amd_lru_plan": (c_int, [_LRUP, c_int64, c_int64, POINTER(c_int32), POINTER(c_int32)]),
+    "sbi_amd_lru_workspace_bytes": (c_int64, [_LRUP, c_int64, c_int64, c_int32]),
+    "sbi_amd_lru_forward": (c_int, [_LRUP, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_lru_backward": (
+        c_int, [_LRUP, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 # include/sbi_amd_cond.h (conditional-density grids: fill, fp64 moments / correlation coefficient, conditioned expand)
 _SIGNATURES_COND = {
     "sbi_amd_cond_grid_fill": (
@@ -535,6 +553,10 @@ def exported_symbols_embed():
 
 def exported_symbols_cnn():
     return list(_SIGNATURES_CNN)
+
+
+def exported_symbols_lru():
+    return list(_SIGNATURES_LRU)
 
 
 def exported_symbols_mmd():
@@ -624,7 +646,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_NPSE_IID, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
                                       **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG,
-                                      **_SIGNATURES_EMBED, **_SIGNATURES_COND, **_SIGNATURES_CNN}.items():
+                                      **_SIGNATURES_EMBED, **_SIGNATURES_COND, **_SIGNATURES_CNN, **_SIGNATURES_LRU}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

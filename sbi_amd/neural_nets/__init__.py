@@ -8,6 +8,9 @@ from sbi_amd.neural_nets.net_builders.flow import build_maf  # noqa: F401,E402
 from sbi_amd.neural_nets.embedding_nets import (  # noqa: F401,E402
     CNNEmbedding,
     FCEmbedding,
+    LRU,
+    LRUBlock,
+    LRUEmbedding,
     PermutationInvariantEmbedding,
     calculate_filter_output_size,
     get_new_cnn_output_size,

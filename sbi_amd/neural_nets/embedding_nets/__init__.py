@@ -5,3 +5,4 @@ from sbi_amd.neural_nets.embedding_nets.cnn import (  # noqa: F401
     calculate_filter_output_size,
     get_new_cnn_output_size,
 )
+from sbi_amd.neural_nets.embedding_nets.lru import LRU, LRUBlock, LRUEmbedding  # noqa: F401
