@@ -47,6 +47,12 @@ int64_t sbi_amd_maf_affine_packed_floats(const sbi_amd_maf_affine_config* cfg);
  * selects its bias vector. */
 int64_t sbi_amd_maf_affine_param_offset(const sbi_amd_maf_affine_config* cfg, int32_t t, int32_t which, int32_t bias);
 
+/* Waves per workgroup (16 rows each) an n-row launch gets, or SBI_AMD_E_*: 8, halved while the rows make fewer than
+ * 256 workgroups, then one fewer at a time until the weight image plus the waves' scratch fit 160 KiB of LDS.
+ * trials == 0: log_prob, sample and the training pass; != 0: log_prob_trials with n thetas (its scratch also holds
+ * the flow states of a block of trials).  Host-side answer, no device call. */
+int32_t sbi_amd_maf_affine_plan_waves(const sbi_amd_maf_affine_config* cfg, int64_t n, int32_t trials);
+
 /* flat params (+ the permutations) -> packed image (masked weights in the MFMA operand layout). */
 int sbi_amd_maf_affine_pack(const sbi_amd_maf_affine_config* cfg, const float* params, const int32_t* perms,
                             float* packed, void* stream);

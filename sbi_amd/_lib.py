@@ -429,6 +429,7 @@ _SIGNATURES_MAF_AFFINE = {
     "sbi_amd_maf_affine_param_count": (c_int64, [_AFFP]),
     "sbi_amd_maf_affine_packed_floats": (c_int64, [_AFFP]),
     "sbi_amd_maf_affine_param_offset": (c_int64, [_AFFP, c_int32, c_int32, c_int32]),
+    "sbi_amd_maf_affine_plan_waves": (c_int32, [_AFFP, c_int64, c_int32]),
     "sbi_amd_maf_affine_pack": (c_int, [_AFFP, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sbi_amd_maf_affine_log_prob": (
         c_int, [_AFFP, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -249,6 +249,14 @@ extern "C" int64_t sbi_amd_maf_affine_param_offset(const sbi_amd_maf_affine_conf
   return (int64_t)t * ap.m.n_layer + (bias ? L.g_b : L.g_w);
 }
 
+extern "C" int32_t sbi_amd_maf_affine_plan_waves(const sbi_amd_maf_affine_config* cfg, int64_t n, int32_t trials) {
+  if (!cfg || n < 1) return SBI_AMD_E_BADARG;
+  MafAffPlan ap;
+  int nw = 0;
+  const int rc = aff_plan_for_rows(cfg, n, trials != 0, &ap, &nw);
+  return rc ? rc : nw;
+}
+
 extern "C" int sbi_amd_maf_affine_pack(const sbi_amd_maf_affine_config* cfg, const float* params,
                                        const int32_t* perms, float* packed, void* stream) {
   if (!cfg || !params || !perms || !packed) return SBI_AMD_E_BADARG;

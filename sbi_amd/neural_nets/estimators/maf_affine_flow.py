@@ -163,6 +163,15 @@ class MAFAffineNet(MAFNet):
             _lib.check(int(need), "maf_affine_train_workspace_floats")
         return int(need)
 
+    def plan_waves(self, n: int, trials: bool = False) -> int:
+        """Waves per workgroup (16 rows each) log_prob, sample and the training pass (``trials``: the iid-trials
+        kernel, ``n`` thetas) launch with for ``n`` rows; a host-side answer, raises where those calls would refuse
+        the configuration."""
+        nw = _lib.load().sbi_amd_maf_affine_plan_waves(self.hyper.c_config(), n, 1 if trials else 0)
+        if nw < 0:
+            _lib.check(int(nw), "maf_affine_plan_waves")
+        return int(nw)
+
     def train_pass(self, theta: Tensor, x: Tensor, row_weight: Optional[Tensor], uniform_weight: float,
                    grad_out: Tensor, workspace: Optional[Tensor] = None, want_grad_theta: bool = False,
                    grad_x_out: Optional[Tensor] = None):

@@ -260,13 +260,13 @@ def _declared():
     return sorted(set(re.findall(r"\b(sbi_amd_\w+)\s*\(", text)))
 
 
-def test_library_exports_the_nine_symbols():
+def test_library_exports_the_ten_symbols():
     _build.build()
     lib = ctypes.CDLL(str(_build.LIB_PATH))
     syms = _declared()
     assert syms == sorted([
         "sbi_amd_maf_affine_param_count", "sbi_amd_maf_affine_packed_floats", "sbi_amd_maf_affine_param_offset",
-        "sbi_amd_maf_affine_pack", "sbi_amd_maf_affine_log_prob", "sbi_amd_maf_affine_sample",
+        "sbi_amd_maf_affine_plan_waves", "sbi_amd_maf_affine_pack", "sbi_amd_maf_affine_log_prob", "sbi_amd_maf_affine_sample",
         "sbi_amd_maf_affine_train_workspace_floats", "sbi_amd_maf_affine_loss_fwd_bwd",
         "sbi_amd_maf_affine_log_prob_trials"])
     for s in syms:
