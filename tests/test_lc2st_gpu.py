@@ -2,9 +2,11 @@
 restatement tests/lc2st_oracle.py on identical row lists, initial weights and epoch orders; determinism and
 independence of the members; the early-stopping bookkeeping; LC2ST / LC2ST_NF end to end on the linear Gaussian.
 
-Shapes (D, Dx, H): the reference's default widths 10 D up to D = 10, and the envelope corners F = 64 and H = 128.
-B = 200: 540 training rows give batches of 200 / 200 / 140 (the last one 4 chunks of 32 + 12 rows), one member has
-exactly one full batch, one has 37 < B rows; validation sets of 60, 33 and 1 rows straddle the 32-row chunk."""
+Shapes (D, Dx, H): the reference's default widths 10 D up to D = 10, and two wide ones, F = 64 with H = 120 and H = 128
+with F = 7.  B = 200: 540 training rows give batches of 200 / 200 / 140 (the last one 4 chunks of 32 + 12 rows), one
+member has exactly one full batch, one has 37 < B rows; validation sets of 60, 33 and 1 rows straddle the 32-row chunk.
+The edges of the 16-wide tiles (F, H and D around a tile, the corner F = 64 with H = 128), the other batch sizes and
+chunk counts, and evaluations of more than one 512-row block are in tests/test_lc2st_envelope_gpu.py."""
 import numpy as np
 import pytest
 import torch
