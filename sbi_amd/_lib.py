@@ -131,6 +131,14 @@ class LRUConfigC(Structure):
                 ("bidirectional", c_int32), ("aggregation", c_int32)]
 
 
+class CausalCNNConfigC(Structure):
+    """Mirror of ``struct sbi_amd_ccnn_config`` (include/sbi_amd_causal_cnn.h)."""
+
+    _fields_ = [("in_channels", c_int32), ("T", c_int32), ("num_conv_layers", c_int32), ("out_channels", c_int32 * 16),
+                ("dilation", c_int32 * 16), ("kernel_size", c_int32), ("pool_kernel_size", c_int32),
+                ("negative_slope", c_float)]
+
+
 _SIGNATURES = {
     "sbi_amd_nsf_param_count": (c_int64, [POINTER(NSFConfigC)]),
     "sbi_amd_nsf_layer_offset": (c_int64, [POINTER(NSFConfigC), c_int32]),
@@ -528,6 +536,16 @@ _SIGNATURES_LRU = {
         c_int, [_LRUP, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_causal_cnn.h (the dilated causal stack + average pool of CausalCNNEmbedding)
+_CCNNP = POINTER(CausalCNNConfigC)
+_SIGNATURES_CAUSAL_CNN = {
+    "sbi_amd_ccnn_param_count": (c_int64, [_CCNNP, POINTER(c_int64)]),
+    "sbi_amd_ccnn_plan": (c_int, [_CCNNP, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "sbi_amd_ccnn_workspace_bytes": (c_int64, [_CCNNP, c_int64]),
+    "sbi_amd_ccnn_forward": (c_int, [_CCNNP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sbi_amd_ccnn_backward": (c_int, [_CCNNP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 # include/sbi_amd_cond.h (conditional-density grids: fill, fp64 moments / correlation coefficient, conditioned expand)
 _SIGNATURES_COND = {
     "sbi_amd_cond_grid_fill": (
@@ -558,6 +576,10 @@ def exported_symbols_cnn():
 
 def exported_symbols_lru():
     return list(_SIGNATURES_LRU)
+
+
+def exported_symbols_causal_cnn():
+    return list(_SIGNATURES_CAUSAL_CNN)
 
 
 def exported_symbols_mmd():
@@ -647,7 +669,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     for name, (restype, argtypes) in {**_SIGNATURES, **_SIGNATURES_NPSE, **_SIGNATURES_NPSE_IID, **_SIGNATURES_LC2ST, **_SIGNATURES_MDN,
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
                                       **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG,
-                                      **_SIGNATURES_EMBED, **_SIGNATURES_COND, **_SIGNATURES_CNN, **_SIGNATURES_LRU}.items():
+                                      **_SIGNATURES_EMBED, **_SIGNATURES_COND, **_SIGNATURES_CNN, **_SIGNATURES_LRU,
+                                      **_SIGNATURES_CAUSAL_CNN}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

@@ -7,11 +7,14 @@ from sbi_amd.neural_nets.net_builders.estimator_configs import (MAFConfig, MAFRQ
 from sbi_amd.neural_nets.net_builders.flow import build_maf  # noqa: F401,E402
 from sbi_amd.neural_nets.embedding_nets import (  # noqa: F401,E402
     CNNEmbedding,
+    CausalCNNEmbedding,
     FCEmbedding,
     LRU,
     LRUBlock,
     LRUEmbedding,
     PermutationInvariantEmbedding,
+    WaveNetSRLikeAggregator,
     calculate_filter_output_size,
+    causalConv1d,
     get_new_cnn_output_size,
 )

@@ -6,3 +6,8 @@ from sbi_amd.neural_nets.embedding_nets.cnn import (  # noqa: F401
     get_new_cnn_output_size,
 )
 from sbi_amd.neural_nets.embedding_nets.lru import LRU, LRUBlock, LRUEmbedding  # noqa: F401
+from sbi_amd.neural_nets.embedding_nets.causal_cnn import (  # noqa: F401
+    CausalCNNEmbedding,
+    WaveNetSRLikeAggregator,
+    causalConv1d,
+)
