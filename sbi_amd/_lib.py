@@ -139,6 +139,13 @@ class CausalCNNConfigC(Structure):
                 ("negative_slope", c_float)]
 
 
+class SCConfigC(Structure):
+    """Mirror of ``struct sbi_amd_sc_config`` (include/sbi_amd_sc.h)."""
+
+    _fields_ = [("in_channels", c_int32), ("conv_channels", c_int32), ("out_channels", c_int32), ("modes", c_int32),
+                ("num_layers", c_int32), ("n_points", c_int32), ("has_positions", c_int32)]
+
+
 _SIGNATURES = {
     "sbi_amd_nsf_param_count": (c_int64, [POINTER(NSFConfigC)]),
     "sbi_amd_nsf_layer_offset": (c_int64, [POINTER(NSFConfigC), c_int32]),
@@ -546,6 +553,20 @@ _SIGNATURES_CAUSAL_CNN = {
     "sbi_amd_ccnn_backward": (c_int, [_CCNNP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_sc.h (SpectralConvEmbedding, the whole module)
+_SCP = POINTER(SCConfigC)
+_SIGNATURES_SC = {
+    "sbi_amd_sc_param_count": (c_int64, [_SCP, POINTER(c_int64)]),
+    "sbi_amd_sc_plan": (c_int, [_SCP, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "sbi_amd_sc_workspace_bytes": (c_int64, [_SCP, c_int64]),
+    "sbi_amd_sc_forward": (
+        c_int, [_SCP, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "sbi_amd_sc_backward": (
+        c_int,
+        [_SCP, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+         c_void_p]),
+}
+
 # include/sbi_amd_cond.h (conditional-density grids: fill, fp64 moments / correlation coefficient, conditioned expand)
 _SIGNATURES_COND = {
     "sbi_amd_cond_grid_fill": (
@@ -580,6 +601,10 @@ def exported_symbols_lru():
 
 def exported_symbols_causal_cnn():
     return list(_SIGNATURES_CAUSAL_CNN)
+
+
+def exported_symbols_sc():
+    return list(_SIGNATURES_SC)
 
 
 def exported_symbols_mmd():
@@ -670,7 +695,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
                                       **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG,
                                       **_SIGNATURES_EMBED, **_SIGNATURES_COND, **_SIGNATURES_CNN, **_SIGNATURES_LRU,
-                                      **_SIGNATURES_CAUSAL_CNN}.items():
+                                      **_SIGNATURES_CAUSAL_CNN, **_SIGNATURES_SC}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

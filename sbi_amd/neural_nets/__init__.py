@@ -13,6 +13,9 @@ from sbi_amd.neural_nets.embedding_nets import (  # noqa: F401,E402
     LRUBlock,
     LRUEmbedding,
     PermutationInvariantEmbedding,
+    SpectralConv1d_SMM,
+    SpectralConvEmbedding,
+    VFT,
     WaveNetSRLikeAggregator,
     calculate_filter_output_size,
     causalConv1d,

@@ -11,3 +11,8 @@ from sbi_amd.neural_nets.embedding_nets.causal_cnn import (  # noqa: F401
     WaveNetSRLikeAggregator,
     causalConv1d,
 )
+from sbi_amd.neural_nets.embedding_nets.sc_embedding import (  # noqa: F401
+    SpectralConv1d_SMM,
+    SpectralConvEmbedding,
+    VFT,
+)
