@@ -4,7 +4,9 @@ routing, and the module in front of a flow.
 
 Parity bound (features and flat real-view parameter gradient, the bound of tests/test_embedding_nets_gpu.py): the
 kernel's worst error against the fp64 oracle is at most 4 x the eager fp32 route's worst error on the same device and
-inputs, with the floor 16 * 2^-24 * max|ref|.  Measured figures go to the parity artifact (tests/parity_log.py)."""
+inputs, with the floor 16 * 2^-24 * max|ref|.  test_parity holds its gradient to the same bound once more in every
+parameter slot on its own (tests/lru_envelope.py, `slot_check`).  Measured figures go to the parity artifact
+(tests/parity_log.py)."""
 import copy
 import functools
 import itertools
@@ -17,7 +19,7 @@ from sbi_amd import _lib
 from sbi_amd.neural_nets import LRUEmbedding
 from sbi_amd.neural_nets.embedding_nets import lru as L
 from tests import lru_embedding_oracle as O
-from tests import parity_log
+from tests import lru_envelope, parity_log
 
 pytestmark = pytest.mark.gpu
 
@@ -130,6 +132,11 @@ def test_parity(case):
     got = run_both(*both_routes(net), x, wts)
     for i, what in enumerate(("forward", "param_grad")):
         check("lru_parity", config, what, got["kernel"][i], got["eager"][i], ref[i])
+    if case[1] <= max(BATCHES):
+        # the gradient slot by slot (tests/lru_envelope.py); the 600 distinct sequences of the grid-wrap case would be
+        # 600 oracle calls, it keeps the whole-vector bound alone
+        _, _, per_seq_abs = lru_envelope.per_sequence(net, x, wts)
+        lru_envelope.slot_check("lru_parity_slots", case, got["kernel"][1], got["eager"][1], ref[1], per_seq_abs)
 
 
 GOLDEN = torch.load(os.path.join(os.path.dirname(__file__), "golden", "lru_embedding_reference.pt"), weights_only=False)
