@@ -567,6 +567,32 @@ _SIGNATURES_SC = {
          c_void_p]),
 }
 
+# include/sbi_amd_tr.h (TransformerEmbedding in series mode)
+class TRConfigC(Structure):
+    """Mirror of ``struct sbi_amd_tr_config`` (include/sbi_amd_tr.h)."""
+
+    _fields_ = [("feature_space_dim", c_int32), ("num_attention_heads", c_int32), ("num_key_value_heads", c_int32),
+                ("head_dim", c_int32), ("intermediate_size", c_int32), ("num_hidden_layers", c_int32),
+                ("final_emb_dimension", c_int32), ("pos_emb", c_int32), ("activation", c_int32),
+                ("is_causal", c_int32), ("scalar_input", c_int32), ("rms_norm_eps", ctypes.c_float),
+                ("div_term", ctypes.c_float * 32)]
+
+
+_TRP = POINTER(TRConfigC)
+_SIGNATURES_TR = {
+    "sbi_amd_tr_param_count": (c_int64, [_TRP, POINTER(c_int64)]),
+    "sbi_amd_tr_plan": (c_int, [_TRP, c_int64, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "sbi_amd_tr_workspace_bytes": (c_int64, [_TRP, c_int64, c_int64, c_int32]),
+    "sbi_amd_tr_forward": (
+        c_int, [_TRP, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, ctypes.c_uint64,
+                c_void_p, c_void_p, c_int32, c_void_p]),
+    "sbi_amd_tr_backward": (
+        c_int, [_TRP, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, ctypes.c_uint64,
+                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sbi_amd_tr_dropout_mask": (
+        c_int, [_TRP, c_int64, c_int64, ctypes.c_float, ctypes.c_uint64, c_int32, c_void_p, c_void_p]),
+}
+
 # include/sbi_amd_cond.h (conditional-density grids: fill, fp64 moments / correlation coefficient, conditioned expand)
 _SIGNATURES_COND = {
     "sbi_amd_cond_grid_fill": (
@@ -695,7 +721,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
                                       **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG,
                                       **_SIGNATURES_EMBED, **_SIGNATURES_COND, **_SIGNATURES_CNN, **_SIGNATURES_LRU,
-                                      **_SIGNATURES_CAUSAL_CNN, **_SIGNATURES_SC}.items():
+                                      **_SIGNATURES_CAUSAL_CNN, **_SIGNATURES_SC, **_SIGNATURES_TR}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

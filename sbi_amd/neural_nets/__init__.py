@@ -9,13 +9,23 @@ from sbi_amd.neural_nets.embedding_nets import (  # noqa: F401,E402
     CNNEmbedding,
     CausalCNNEmbedding,
     FCEmbedding,
+    FullAttention,
+    IdentityEncoder,
     LRU,
     LRUBlock,
     LRUEmbedding,
+    MLP,
+    MoeBlock,
     PermutationInvariantEmbedding,
+    PositionalEncoder,
+    RMSNorm,
+    RotaryEncoder,
     SpectralConv1d_SMM,
     SpectralConvEmbedding,
+    TransformerBlock,
+    TransformerEmbedding,
     VFT,
+    ViTEmbeddings,
     WaveNetSRLikeAggregator,
     calculate_filter_output_size,
     causalConv1d,

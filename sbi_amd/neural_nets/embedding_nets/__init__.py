@@ -16,3 +16,15 @@ from sbi_amd.neural_nets.embedding_nets.sc_embedding import (  # noqa: F401
     SpectralConvEmbedding,
     VFT,
 )
+from sbi_amd.neural_nets.embedding_nets.transformer import (  # noqa: F401
+    FullAttention,
+    IdentityEncoder,
+    MLP,
+    MoeBlock,
+    PositionalEncoder,
+    RMSNorm,
+    RotaryEncoder,
+    TransformerBlock,
+    TransformerEmbedding,
+    ViTEmbeddings,
+)
