@@ -593,6 +593,23 @@ _SIGNATURES_TR = {
         c_int, [_TRP, c_int64, c_int64, ctypes.c_float, ctypes.c_uint64, c_int32, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_resnet.h (the trunk of ResNetEmbedding1D)
+class ResNetConfigC(Structure):
+    """Mirror of ``struct sbi_amd_resnet_config`` (include/sbi_amd_resnet.h)."""
+
+    _fields_ = [("c_in", c_int32), ("c_internal", c_int32), ("c_hidden", c_int32), ("n_blocks", c_int32)]
+
+
+_RNP = POINTER(ResNetConfigC)
+_SIGNATURES_RESNET = {
+    "sbi_amd_resnet_param_count": (c_int64, [_RNP, POINTER(c_int64)]),
+    "sbi_amd_resnet_plan": (c_int, [_RNP, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "sbi_amd_resnet_workspace_bytes": (c_int64, [_RNP, c_int64, c_int32]),
+    "sbi_amd_resnet_forward": (c_int, [_RNP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
+    "sbi_amd_resnet_backward": (
+        c_int, [_RNP, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 # include/sbi_amd_cond.h (conditional-density grids: fill, fp64 moments / correlation coefficient, conditioned expand)
 _SIGNATURES_COND = {
     "sbi_amd_cond_grid_fill": (
@@ -631,6 +648,10 @@ def exported_symbols_causal_cnn():
 
 def exported_symbols_sc():
     return list(_SIGNATURES_SC)
+
+
+def exported_symbols_resnet():
+    return list(_SIGNATURES_RESNET)
 
 
 def exported_symbols_mmd():
@@ -721,7 +742,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
                                       **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG,
                                       **_SIGNATURES_EMBED, **_SIGNATURES_COND, **_SIGNATURES_CNN, **_SIGNATURES_LRU,
-                                      **_SIGNATURES_CAUSAL_CNN, **_SIGNATURES_SC, **_SIGNATURES_TR}.items():
+                                      **_SIGNATURES_CAUSAL_CNN, **_SIGNATURES_SC, **_SIGNATURES_TR, **_SIGNATURES_RESNET}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

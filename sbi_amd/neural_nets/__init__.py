@@ -19,6 +19,9 @@ from sbi_amd.neural_nets.embedding_nets import (  # noqa: F401,E402
     PermutationInvariantEmbedding,
     PositionalEncoder,
     RMSNorm,
+    ResNetEmbedding1D,
+    ResNetEmbedding2D,
+    ResidualBLock,
     RotaryEncoder,
     SpectralConv1d_SMM,
     SpectralConvEmbedding,
@@ -29,5 +32,8 @@ from sbi_amd.neural_nets.embedding_nets import (  # noqa: F401,E402
     WaveNetSRLikeAggregator,
     calculate_filter_output_size,
     causalConv1d,
+    construct_simple_conv_net,
+    construct_simple_fc_net,
     get_new_cnn_output_size,
+    zero_pad,
 )

@@ -28,3 +28,11 @@ from sbi_amd.neural_nets.embedding_nets.transformer import (  # noqa: F401
     TransformerEmbedding,
     ViTEmbeddings,
 )
+from sbi_amd.neural_nets.embedding_nets.resnet import (  # noqa: F401
+    ResNetEmbedding1D,
+    ResNetEmbedding2D,
+    ResidualBLock,
+    construct_simple_conv_net,
+    construct_simple_fc_net,
+    zero_pad,
+)
