@@ -30,12 +30,15 @@
  *   - Dropout: the keep decision of (layer, b, head, q, k) is word k & 3 of Philox-4x32-10 with key = seed and counter
  *     (k >> 2, q, b, layer H + head); kept when the uniform is >= p.
  *   - Forward: input kernel, then per block norm+qkv, attention, block tail; one final kernel on the last tokens.
- *   - Backward: final kernel, then per block in reverse: tail backward, attention backward (dq with D = rowsum(dO o O),
- *     then dk / dv per key, query heads of a shared head in ascending order), qkv backward.  Probabilities are rebuilt
- *     as exp(S - lse), the norms and the gated activation inside the tile.
+ *   - Backward: final kernel, then per block in reverse: tail backward, attention backward (dq with D = sum_k P dP,
+ *     taken as the P-weighted mean of dP around key 0's so that a one-key row gives dP - D = 0 exactly, dP = dO . v
+ *     summed in fp64 and rounded once; then dk / dv
+ *     per key, the query heads of a shared head as four chains), qkv backward.  Probabilities are rebuilt as
+ *     exp(S - lse), the norms and the gated activation inside the tile.
  *   - Weight gradients: workgroup g of G = ceil(tiles / ceil(tiles / TR_MAX_PARTIALS)) walks a contiguous range of
  *     tiles and adds each tile's product into its own partial image in the workspace (thread-owned elements, no
- *     atomics); a second kernel adds the at most TR_MAX_PARTIALS = 256 partials in workgroup order.
+ *     atomics); a second kernel adds the at most TR_MAX_PARTIALS = 256 partials as four chains over the workgroups;
+ *     norm.weight and the aggregator's gradients are four chains over the sequences.
  *
  * Semantics.  No float atomics: every sum has an order fixed by (config, B, T).  A sequence's output row is bitwise the
  * same alone, anywhere in a batch and at any B (with dropout: at the same batch index and seed).  Two backward calls

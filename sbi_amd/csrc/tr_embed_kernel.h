@@ -213,6 +213,13 @@ __device__ __forceinline__ float tr_dot(const float* a, int sa, const float* b, 
     if (i + c < n) acc[c] = fmaf(a[(int64_t)(i + c) * sa], b[(int64_t)(i + c) * sb], acc[c]);
   return TR_JOIN(acc);
 }
+// sum_i a[i] b[i], i < n, rounded once: fp32 products are exact in fp64 and n <= 64 terms lose nothing that fp32 keeps.
+// For dP = dO . v in the attention backward, whose terms cancel: dS = P (dP - D) is held relative to dS, not to |dO| |v|.
+__device__ __forceinline__ float tr_dot_wide(const float* a, const float* b, int n) {
+  double acc = 0.0;
+  for (int i = 0; i < n; ++i) acc = fma((double)a[i], (double)b[i], acc);
+  return (float)acc;
+}
 // partial[j K + k] (+)= sum_t A[t lda + j] Bm[t ldb + k], t ascending: thread-owned elements of the workgroup's image
 __device__ __forceinline__ void tr_tile_wgrad(float* __restrict__ partial, const float* A, int lda, const float* Bm,
                                               int ldb, int J, int K, bool first) {
@@ -474,23 +481,20 @@ __global__ __launch_bounds__(128) void tr_final_bwd_kernel(TrPlan pl, TrArgs a) 
     a.dh[(b * a.T + a.T - 1) * F + f] = rs * (dy[f] * a.params[pl.p_norm + f] - xh[f] * cm);
   }
 }
-// norm.weight, aggregator.weight, aggregator.bias: one thread per element, the sequences in ascending order
+// norm.weight, aggregator.weight, aggregator.bias: one thread per element, the sequences as four chains
 __global__ __launch_bounds__(TR_THREADS) void tr_final_wgrad_kernel(TrPlan pl, TrArgs a) {
   const int F = pl.F, E = pl.E;
   const int e = blockIdx.x * TR_THREADS + threadIdx.x;
   if (e >= F + E * F + E) return;
-  float s = 0.f;
+  const float one = 1.0f;
   if (e < F) {
-    for (int64_t b = 0; b < a.B; ++b) s += a.cbuf[b * F + e];
-    a.grad[pl.p_norm + e] = s;
+    a.grad[pl.p_norm + e] = tr_dot(a.cbuf + e, F, &one, 0, (int)a.B);
   } else if (e < F + E * F) {
     const int o = (e - F) / F, f = (e - F) % F;
-    for (int64_t b = 0; b < a.B; ++b) s = fmaf(a.gout[b * E + o], a.ybuf[b * F + f], s);
-    a.grad[pl.p_aggw + e - F] = s;
+    a.grad[pl.p_aggw + e - F] = tr_dot(a.gout + o, E, a.ybuf + f, F, (int)a.B);
   } else {
     const int o = e - F - E * F;
-    for (int64_t b = 0; b < a.B; ++b) s += a.gout[b * E + o];
-    a.grad[pl.p_aggb + o] = s;
+    a.grad[pl.p_aggb + o] = tr_dot(a.gout + o, E, &one, 0, (int)a.B);
   }
 }
 
@@ -562,7 +566,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_tail_bwd_kernel(TrPlan pl, TrAr
   }
 }
 
-// one wave per (b, head, query): D = rowsum(dO o O) and d q
+// one wave per (b, head, query): D = sum_k P dP and d q
 __global__ __launch_bounds__(TR_THREADS) void tr_attn_bwd_dq_kernel(TrPlan pl, TrArgs a) {
   extern __shared__ float lds[];
   const int hd = pl.hd, T = (int)a.T;
@@ -581,25 +585,35 @@ __global__ __launch_bounds__(TR_THREADS) void tr_attn_bwd_dq_kernel(TrPlan pl, T
   const float* kp = a.k + (b * pl.KV + kvh) * (int64_t)T * hd;
   const float* vp = a.v + (b * pl.KV + kvh) * (int64_t)T * hd;
   const int64_t orow = (b * T + q) * pl.F + head * hd;
-  float prod = 0.f;
   if (lane < hd) {
     qs[lane] = a.q[wc * hd + lane];
     dos[lane] = a.dO[orow + lane];
-    prod = dos[lane] * a.attn[orow + lane];
   }
-  const float Dv = tr_wave_sum(prod);
-  if (active && lane == 0) a.D[w] = Dv;
   __syncthreads();
   const float lse = a.lse[wc];
   const int lh = a.layer * pl.H + head;
+  // D = rowsum(dO o O) = sum_k P[k] dP[k], taken as the P-weighted mean of dP around key 0's: its error is relative
+  // to the spread of dP over the row, not to |dO| |O|, a common factor of the rebuilt P cancels, and a row with one
+  // key gives dP - D = 0 exactly, as its softmax demands.
+  float ref = tr_dot_wide(dos, vp, hd);
+  if (a.p > 0.f) ref = tr_keep(a.seed_lo, a.seed_hi, lh, (int)b, q, 0, a.p) ? ref * a.inv_keep : 0.f;
+  float num = 0.f, den = 0.f;
   for (int k = lane; k < nk; k += 64) {
     const float s = tr_dot(qs, 1, kp + (int64_t)k * hd, 1, hd);
-    const float dp = tr_dot(dos, 1, vp + (int64_t)k * hd, 1, hd);
+    const float dp = tr_dot_wide(dos, vp + (int64_t)k * hd, hd);
     const float p = expf(s * pl.scale - lse);
-    float kf = 1.0f;
-    if (a.p > 0.f) kf = tr_keep(a.seed_lo, a.seed_hi, lh, (int)b, q, k, a.p) ? a.inv_keep : 0.f;
-    ds[k] = p * (kf * dp - Dv);
+    float pd = dp;
+    if (a.p > 0.f) pd = tr_keep(a.seed_lo, a.seed_hi, lh, (int)b, q, k, a.p) ? dp * a.inv_keep : 0.f;
+    ds[k] = p;
+    ds[T + k] = pd;
+    num = fmaf(p, pd - ref, num);
+    den += p;
   }
+  num = tr_wave_sum(num);
+  den = tr_wave_sum(den);
+  const float Dv = den > 0.f ? ref + num / den : ref;
+  if (active && lane == 0) a.D[w] = Dv;
+  for (int k = lane; k < nk; k += 64) ds[k] = ds[k] * (ds[T + k] - Dv);
   __syncthreads();
   if (active && lane < hd) {
     a.dq[wc * hd + lane] = tr_dot(ds, 1, kp + lane, hd, nk) * pl.scale;
@@ -626,7 +640,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_attn_bwd_dkv_kernel(TrPlan pl, 
     ks[lane] = a.k[wc * hd + lane];
     vs[lane] = a.v[wc * hd + lane];
   }
-  float accK = 0.f, accV = 0.f;
+  float accK[4] = {0.f, 0.f, 0.f, 0.f}, accV[4] = {0.f, 0.f, 0.f, 0.f};      // the group's heads as four chains
   for (int g = 0; g < pl.group; ++g) {
     const int head = kvh * pl.group + g;
     const int lh = a.layer * pl.H + head;
@@ -637,22 +651,26 @@ __global__ __launch_bounds__(TR_THREADS) void tr_attn_bwd_dkv_kernel(TrPlan pl, 
     __syncthreads();
     for (int q = q0 + lane; q < T; q += 64) {
       const float s = tr_dot(qp + (int64_t)q * hd, 1, ks, 1, hd);
-      const float dp = tr_dot(dop + (int64_t)q * pl.F, 1, vs, 1, hd);
+      const float dp = tr_dot_wide(dop + (int64_t)q * pl.F, vs, hd);
       const float p = expf(s * pl.scale - lsep[q]);
       float kf = 1.0f;
       if (a.p > 0.f) kf = tr_keep(a.seed_lo, a.seed_hi, lh, (int)b, q, j, a.p) ? a.inv_keep : 0.f;
-      ds[q] = p * (kf * dp - Dp[q]);
+      ds[q] = p * ((a.p > 0.f ? dp * kf : dp) - Dp[q]);
       pd[q] = p * kf;
     }
     __syncthreads();
     if (lane < hd) {
-      accK += tr_dot(ds + q0, 1, qp + (int64_t)q0 * hd + lane, hd, T - q0);
-      accV += tr_dot(pd + q0, 1, dop + (int64_t)q0 * pl.F + lane, pl.F, T - q0);
+      const float dK = tr_dot(ds + q0, 1, qp + (int64_t)q0 * hd + lane, hd, T - q0);
+      const float dV = tr_dot(pd + q0, 1, dop + (int64_t)q0 * pl.F + lane, pl.F, T - q0);
+      if ((g & 3) == 0) { accK[0] += dK; accV[0] += dV; }
+      else if ((g & 3) == 1) { accK[1] += dK; accV[1] += dV; }
+      else if ((g & 3) == 2) { accK[2] += dK; accV[2] += dV; }
+      else { accK[3] += dK; accV[3] += dV; }
     }
   }
   if (active && lane < hd) {
-    a.dk[wc * hd + lane] = accK * pl.scale;
-    a.dv[wc * hd + lane] = accV;
+    a.dk[wc * hd + lane] = TR_JOIN(accK) * pl.scale;
+    a.dv[wc * hd + lane] = TR_JOIN(accV);
   }
 }
 
@@ -741,14 +759,13 @@ __global__ __launch_bounds__(TR_THREADS) void tr_qkv_bwd_kernel(TrPlan pl, TrArg
   }
 }
 
-// dst[i] = sum_g partial[g stride + src0 + i], g ascending
+// dst[i] = sum_g partial[g stride + src0 + i], the workgroups as four chains
 __global__ __launch_bounds__(TR_THREADS) void tr_reduce_kernel(const float* __restrict__ partial, int G, int stride,
                                                                int src0, int n, float* __restrict__ dst) {
   const int i = blockIdx.x * TR_THREADS + threadIdx.x;
   if (i >= n) return;
-  float s = 0.f;
-  for (int g = 0; g < G; ++g) s += partial[(int64_t)g * stride + src0 + i];
-  dst[i] = s;
+  const float one = 1.0f;
+  dst[i] = tr_dot(partial + src0 + i, stride, &one, 0, G);
 }
 
 __global__ __launch_bounds__(TR_THREADS) void tr_mask_kernel(TrPlan pl, TrArgs a, uint8_t* keep) {

@@ -93,10 +93,11 @@ def vit_tokens(x, p, cfg):
     return emb + torch.cat((table[:, :1], grid), dim=1)
 
 
-def forward(p, x, kwargs, keep_masks=None, attention_mask=None, gates=None, positive=None):
+def forward(p, x, kwargs, keep_masks=None, attention_mask=None, gates=None, positive=None, scores=None):
     """p: {key: fp64 tensor}; x fp64; returns out (B, E) in fp64.  `gates`: a list that receives every block's gate
     pre-activations (the arguments of the activation).  `positive`: one boolean (B, T, I) tensor per block, the side of
-    the kink every relu unit is differentiated on (see `kink_candidates`)."""
+    the kink every relu unit is differentiated on (see `kink_candidates`).  `scores`: a list that receives every
+    block's scaled scores S (B, H, T, T), 0 on the masked keys."""
     cfg = full_config(kwargs)
     H, KV, hd, eps = cfg["num_attention_heads"], cfg["num_key_value_heads"], cfg["head_dim"], cfg["rms_norm_eps"]
     if cfg["vit"]:
@@ -128,6 +129,8 @@ def forward(p, x, kwargs, keep_masks=None, attention_mask=None, gates=None, posi
         v = v.repeat_interleave(H // KV, dim=1)
         s = q @ k.transpose(2, 3) / math.sqrt(hd)
         rows_open = allowed.any(-1, keepdim=True)
+        if scores is not None:
+            scores.append(torch.where(allowed & rows_open, s, torch.zeros_like(s)).detach())
         # a masked score is s + finfo.min == finfo.min in fp32: weight 0 next to an open key, and a row masked
         # everywhere has equal scores, uniform weights over ALL keys
         s = torch.where(rows_open, s.masked_fill(~allowed, -math.inf), torch.zeros_like(s))
