@@ -34,9 +34,10 @@ def _n_blocks(sd) -> int:
     return 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
 
 
-def forward_1d(sd: Dict[str, Tensor], x: Tensor, kwargs: dict, pre: Optional[List[Tensor]] = None
-               ) -> Tuple[Tensor, Tensor]:
-    """(trunk, out) in the dtype of `sd`; `pre` collects every activation's input (rows first)"""
+def forward_1d(sd: Dict[str, Tensor], x: Tensor, kwargs: dict, pre: Optional[List[Tensor]] = None,
+               operands: Optional[Dict[str, Tuple[Tensor, Tensor]]] = None) -> Tuple[Tensor, Tensor]:
+    """(trunk, out) in the dtype of `sd`; `pre` collects every activation's input (rows first); `operands` collects per
+    Linear (its name without ".weight") the pair (input, output)"""
     act = _act(kwargs)
 
     def a(t):
@@ -44,18 +45,24 @@ def forward_1d(sd: Dict[str, Tensor], x: Tensor, kwargs: dict, pre: Optional[Lis
             pre.append(t)
         return act(t)
 
+    def lin(name, t):
+        z = t @ sd[name + ".weight"].T + sd[name + ".bias"]
+        if operands is not None:
+            operands[name] = (t, z)
+        return z
+
     h = x
     if "initial.weight" in sd:
-        h = h @ sd["initial.weight"].T + sd["initial.bias"]
+        h = lin("initial", h)
     for i in range(_n_blocks(sd)):
         p = f"blocks.{i}.f."
-        u = a(h @ sd[p + "0.weight"].T + sd[p + "0.bias"])
-        u = a(u @ sd[p + "2.weight"].T + sd[p + "2.bias"])
-        h = a(u @ sd[p + "4.weight"].T + sd[p + "4.bias"] + h)
+        u = a(lin(p + "0", h))
+        u = a(lin(p + "2", u))
+        h = a(lin(p + "4", u) + h)
     trunk = h
-    u = a(h @ sd["final.0.weight"].T + sd["final.0.bias"])
-    u = a(u @ sd["final.2.weight"].T + sd["final.2.bias"])
-    return trunk, u @ sd["final.4.weight"].T + sd["final.4.bias"]
+    u = a(lin("final.0", h))
+    u = a(lin("final.2", u))
+    return trunk, lin("final.4", u)
 
 
 def forward_2d(sd: Dict[str, Tensor], x: Tensor, kwargs: dict) -> Tensor:
@@ -99,6 +106,23 @@ def reference(state_dict: Dict[str, Tensor], x: Tensor, wts: Tensor, kwargs: dic
     grads = torch.autograd.grad((out * wts.detach().double().cpu()).sum(), list(sd.values()), allow_unused=True)
     flat = torch.cat([(g if g is not None else torch.zeros_like(v)).reshape(-1) for g, v in zip(grads, sd.values())])
     return (None if trunk is None else trunk.detach()), out.detach(), flat
+
+
+def reference_with_operands(state_dict: Dict[str, Tensor], x: Tensor, wts: Tensor, kwargs: dict
+                            ) -> Tuple[Tensor, Tensor, Tensor, Dict[str, Tuple[Tensor, Tensor]]]:
+    """`reference` of a 1D net, and per Linear (its name without ".weight") the fp64 pair (A, D): its input (rows, K) and
+    the gradient of sum(out * wts) with respect to its output (rows, N).  Row r alone contributes the outer product
+    D[r]^T A[r] to the weight's gradient and D[r] to the bias's."""
+    sd = _leaves({k: v.cpu() for k, v in state_dict.items()})
+    operands: Dict[str, Tuple[Tensor, Tensor]] = {}
+    trunk, out = forward_1d(sd, x.detach().double().cpu(), kwargs, operands=operands)
+    outputs = [z for _, z in operands.values()]
+    grads = torch.autograd.grad((out * wts.detach().double().cpu()).sum(), list(sd.values()) + outputs,
+                                allow_unused=True)
+    grads = [torch.zeros_like(v) if g is None else g for g, v in zip(grads, list(sd.values()) + outputs)]
+    flat = torch.cat([g.reshape(-1) for g in grads[:len(sd)]])
+    pairs = {name: (a.detach(), d) for (name, (a, _)), d in zip(operands.items(), grads[len(sd):])}
+    return trunk.detach(), out.detach(), flat, pairs
 
 
 def near_kink_rows(state_dict: Dict[str, Tensor], x: Tensor, kwargs: dict) -> List[int]:

@@ -2,7 +2,8 @@
 
 Bound, for the trunk output, the module output and the flat parameter gradient: the kernel route's worst error against
 the oracle is at most max(4 x the eager fp32 route's worst error on the same device and inputs, 16 * 2^-24 * max|ref|).
-Measured figures go to the parity artifact (tests/parity_log.py).
+Measured figures go to the parity artifact (tests/parity_log.py).  `test_parity` and the recorded 1D cases hold the
+gradient to the same bound once more per parameter tensor, with the scale of tests/resnet_envelope.py (`slot_check`).
 
 Kinks.  A ReLU net's gradient jumps where an activation's input crosses 0, and an fp32 route may land on the other side
 of one that the oracle sees within rounding of 0.  The rows that `near_kink_rows` returns -- decided by the fp64 oracle
@@ -146,10 +147,18 @@ def run_both(net, twin, x, wts):
     return got
 
 
-def parity(test, config, net, x, wts, ref):
+def parity(test, config, net, x, wts, ref, kwargs=None):
+    """`check` for the trunk, the output and the whole flat gradient; with the constructor's `kwargs` also the per-slot
+    bound of tests/resnet_envelope.py for the gradient (its scale from the oracle's operands)"""
+    from tests import resnet_envelope as env
+
     got = run_both(*both_routes(net), x, wts)
     for i, what in enumerate(("trunk", "forward", "param_grad")):
         check(test, config, what, got["kernel"][i], got["eager"][i], ref[i])
+    if kwargs is not None:
+        sd = net.state_dict()
+        scale = env.scale_of(sd, O.reference_with_operands(sd, x, wts, {})[3])
+        env.slot_check(test, (config, env.sizes_of_kwargs(kwargs)), got["kernel"][2], got["eager"][2], ref[2], scale)
 
 
 # ---- parity -----------------------------------------------------------------------------------------------------------
@@ -176,7 +185,7 @@ def test_parity(case):
     net, x, wts, near, ref = draw(case)
     print(f"resnet_parity[{case_id(case)}] rows within the margin of a kink: {len(near)} of {case[0]}")
     assert 3 * len(near) <= case[0], (len(near), case[0])
-    parity("resnet_parity", case_id(case), net, x, wts, ref)
+    parity("resnet_parity", case_id(case), net, x, wts, ref, kwargs_of(case))
 
 
 GOLDEN = torch.load(os.path.join(os.path.dirname(__file__), "golden", "resnet_embedding_reference.pt"),
@@ -193,7 +202,7 @@ def test_the_recorded_1d_cases_on_the_kernel_route(name):
     assert 3 * len(near) <= c["x"].shape[0]
     wts = c["wts"].clone()
     wts[near] = 0
-    parity("resnet_golden", name, net, c["x"], wts, O.reference(c["state_dict"], c["x"], wts, {}))
+    parity("resnet_golden", name, net, c["x"], wts, O.reference(c["state_dict"], c["x"], wts, {}), c["kwargs"])
     if not near:        # the recording itself, within the reference's own fp32 error (tests/test_resnet_embedding_cpu.py)
         kernel = both_routes(net)[0]
         out = kernel(c["x"].cuda())
