@@ -14,7 +14,7 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB_PATH = Path(__file__).resolve().parent / "libsbi_amd_nsf.so"
 SOURCES = ["nsf_plan.cpp", "nsf_flow.hip", "nsf_flow_inv.hip", "nsf_trials.hip", "nsf_train.hip", "nsf_train_k4.hip", "nsf_train_k5.hip", "nsf_train_k8.hip", "nsf_train_k16.hip", "fmpe.hip", "ode.hip",
-           "adam.hip", "spline_abi.hip", "step_tail.hip", "shuffle.hip", "compact.hip", "allreduce.hip", "atomic.hip", "mcmc_slice.hip", "nsf_gtrain.hip", "nsf_coop_plan.cpp", "nsf_coop.hip", "nsf_coop_k4.hip", "nsf_coop_k5.hip", "nsf_coop_k8.hip", "nsf_coop_k16.hip", "maf.hip", "maf_k4.hip", "maf_k5.hip", "maf_k8.hip", "maf_k16.hip", "maf_affine.hip", "nre.hip", "nre_mcmc.hip", "npse.hip", "lc2st.hip", "mdn.hip", "mnle.hip", "mnle_k4.hip", "mnle_k5.hip", "mnle_k8.hip", "mnle_k10.hip", "mnle_k16.hip", "sir.hip", "mmd.hip", "mixture_lse.hip", "sinkhorn.hip", "mog.hip", "embed.hip", "cond_grid.hip", "cnn_embed.hip", "lru_embed.hip", "causal_cnn.hip", "sc_embed.hip", "tr_embed.hip", "resnet_embed.hip"]
+           "adam.hip", "spline_abi.hip", "step_tail.hip", "shuffle.hip", "compact.hip", "allreduce.hip", "atomic.hip", "mcmc_slice.hip", "nsf_gtrain.hip", "nsf_coop_plan.cpp", "nsf_coop.hip", "nsf_coop_k4.hip", "nsf_coop_k5.hip", "nsf_coop_k8.hip", "nsf_coop_k16.hip", "maf.hip", "maf_k4.hip", "maf_k5.hip", "maf_k8.hip", "maf_k16.hip", "maf_affine.hip", "nre.hip", "nre_mcmc.hip", "npse.hip", "lc2st.hip", "mdn.hip", "mnle.hip", "mnle_k4.hip", "mnle_k5.hip", "mnle_k8.hip", "mnle_k10.hip", "mnle_k16.hip", "sir.hip", "mmd.hip", "mixture_lse.hip", "sinkhorn.hip", "mog.hip", "embed.hip", "cond_grid.hip", "cnn_embed.hip", "lru_embed.hip", "causal_cnn.hip", "sc_embed.hip", "tr_embed.hip", "resnet_embed.hip", "vi_gauss.hip"]
 # every header, derived rather than listed: a new or moved header can never fall out of source_hash()
 HEADERS = sorted(CSRC.rglob("*.h")) + sorted((CSRC.parents[1] / "include").glob("*.h"))
 HASH_PATH = LIB_PATH.with_suffix(".so.srchash")   # travels with the .so (git-ignored, not gpurun-ignored)

@@ -467,6 +467,28 @@ _SIGNATURES_SIR = {
          c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sbi_amd_vi.h (the Gaussian variational family of VIPosterior: draw, log_prob, one optimiser iteration)
+class VIConfigC(Structure):
+    """Mirror of ``struct sbi_amd_vi_config`` (include/sbi_amd_vi.h)."""
+
+    _fields_ = [("D", c_int32), ("full_cov", c_int32), ("method", c_int32), ("K", c_int32),
+                ("stick_the_landing", c_int32), ("dreg", c_int32), ("unbiased", c_int32), ("alpha", c_float)]
+
+
+_SIGNATURES_VI = {
+    "sbi_amd_vi_gauss_plan": (c_int, [c_int32, c_int64, POINTER(c_int64)]),
+    "sbi_amd_vi_gauss_draw": (
+        c_int,
+        [c_int32, c_int32, c_void_p, c_void_p, c_int64, c_uint64, ctypes.c_uint32, c_uint64, c_void_p, c_void_p,
+         c_void_p, c_void_p]),
+    "sbi_amd_vi_gauss_log_prob": (c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sbi_amd_vi_gauss_step": (
+        c_int,
+        [POINTER(VIConfigC), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+         c_float, c_float, c_float, c_float, c_int64, c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_int32,
+         c_void_p, c_void_p, c_void_p]),
+}
+
 # include/sbi_amd_mmd.h (RBF-kernel two-sample sums: the misspecification test's permutation baseline, the MMD metrics)
 _SIGNATURES_MMD = {
     "sbi_amd_mmd_rbf_splits": (
@@ -662,6 +684,10 @@ def exported_symbols_abc():
     return list(_SIGNATURES_ABC)
 
 
+def exported_symbols_vi():
+    return list(_SIGNATURES_VI)
+
+
 def exported_symbols_sir():
     return list(_SIGNATURES_SIR)
 
@@ -742,7 +768,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                                       **_SIGNATURES_MNLE, **_SIGNATURES_MAF_AFFINE, **_SIGNATURES_SIR,
                                       **_SIGNATURES_MMD, **_SIGNATURES_ABC, **_SIGNATURES_MOG,
                                       **_SIGNATURES_EMBED, **_SIGNATURES_COND, **_SIGNATURES_CNN, **_SIGNATURES_LRU,
-                                      **_SIGNATURES_CAUSAL_CNN, **_SIGNATURES_SC, **_SIGNATURES_TR, **_SIGNATURES_RESNET}.items():
+                                      **_SIGNATURES_CAUSAL_CNN, **_SIGNATURES_SC, **_SIGNATURES_TR, **_SIGNATURES_RESNET,
+                                      **_SIGNATURES_VI}.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes

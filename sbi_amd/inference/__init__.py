@@ -3,6 +3,7 @@ from sbi_amd.inference.posteriors.importance_posterior import ImportanceSampling
 from sbi_amd.inference.posteriors.mcmc_posterior import MCMCPosterior  # noqa: F401
 from sbi_amd.inference.posteriors.npe_a_posterior import NPE_A_Posterior  # noqa: F401
 from sbi_amd.inference.posteriors.rejection_posterior import RejectionPosterior  # noqa: F401
+from sbi_amd.inference.posteriors.vi_posterior import VIPosterior  # noqa: F401
 from sbi_amd.inference.trainers.nle.mnle import MNLE  # noqa: F401
 from sbi_amd.inference.trainers.nle.nle import NLE, NLE_A, SNLE  # noqa: F401
 from sbi_amd.inference.trainers.npe.npe import NPE, NPE_C, SNPE  # noqa: F401

@@ -1,0 +1,1 @@
+from sbi_amd.inference.posteriors.vi_posterior import VIPosterior  # noqa: F401

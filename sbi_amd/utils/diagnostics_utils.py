@@ -2,8 +2,8 @@
 
 `posterior.sample_batched` does the work wherever it exists: every posterior kind here has one except the rejection
 posterior.  When it raises NotImplementedError or AssertionError (a sampler method that is not vectorised), the
-observations are sampled one after the other in this process: no joblib, no worker processes.  A VIPosterior has no
-counterpart here.
+observations are sampled one after the other in this process: no joblib, no worker processes.  A VIPosterior
+(single-x: its `sample_batched` raises NotImplementedError) takes that loop and samples only at the x it was trained on.
 """
 
 from __future__ import annotations
